@@ -16,9 +16,14 @@ N>1 (families are independent → no collective on the data path):
                     SO:unsorted in input order, so rank order IS file order).  `root` also times a second loop in which
                     every step ships the payloads to rank 0 in rank order over RCCL point-to-point — the north star's
                     single-writer reassembly — and reports it beside (`value_with_reassembly_on_root`): one root receiving
-                    9 GB per rank and step is bound by its xGMI links, not by the kernels.  `auto` (default) = root beyond one rank.
+                    9 GB per rank and step is bound by its xGMI links, not by the kernels.  `auto` (default) = root beyond one rank with --full.
                     The gather loops run LAST, after everything else of the line has been measured, under a watchdog: a rank that
                     fails or hangs in the gather costs `reassemble_error`, never the line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the benchmark measures runs only with
+  --full            the strong-scaling reading (`strong_scaling`), one rank's share of an 8-way run (`share_of_8`), the file -> file leg
+                    (`end_to_end`), the CPU baselines (`cpu_baseline`) and, N>1, the gather to rank 0 (`--reassemble auto` = root)
+  --dump-outputs DIR  after the timed steps, what the last step handed its caller, as float arrays in DIR/<name>.npy (see dump_outputs)
 """
 import argparse
 import glob
@@ -34,6 +39,56 @@ HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 F64_LANE_OPS_PER_S = 64 * 1024 * 2.4e9 / 4   # one f64 add per lane per 4 cycles, 1024 SIMDs at 2.4 GHz = 39.3 T/s
 E2E_CHUNK_MB = 512              # compressed bytes per chunk of the file -> file leg (FGX_BENCH_E2E_CHUNK_MB; tools/e2e_chunk_sweep.py)
 F64_OPS_PER_OBSERVATION = 8     # two Kahan chains (the base seen, any other base) x 4 dependent add/sub
+DUMP_SEED = 20240917            # --dump-outputs: the sampled windows of the record stream
+DUMP_WINDOWS, DUMP_WINDOW_BYTES = 8192, 1024     # 32 MiB of float32
+DUMP_BLOCK_BYTES = 4 << 20      # one pair of sums per 4 MiB block of the record stream
+DUMP_MAX_DEFERRED = 1 << 20     # 8 MiB of float64
+
+
+def dump_window_offsets(n):
+    """Start offsets of the sampled windows of an `n`-byte record stream: seeded, so two builds that produce the same stream sample
+    the same bytes."""
+    import numpy as np
+    w = min(DUMP_WINDOW_BYTES, n)
+    u = np.random.default_rng(DUMP_SEED).random(DUMP_WINDOWS)
+    return np.sort((u * (n - w + 1)).astype(np.int64)), w
+
+
+def dump_outputs(directory, out, stats, prefix=""):
+    """What the timed path hands its caller, from its last step, as float arrays for an output-for-output comparison of two builds
+    (the record stream itself is ~9 GB at the default size, so it is sampled and summed rather than copied; no file is written empty):
+      counters.npy        float64: consensus records, stream bytes, deferred families, then the 28 batch counters (fgx_output.stats)
+      record_windows.npy  float32 [8192, min(1024, bytes)]: the stream's bytes in windows starting at seeded offsets (window_offsets.npy, float64)
+      block_sums.npy      float64 [blocks, 2]: per 4 MiB block of the stream, the sum of its bytes and the sum of byte x (i % 251 + 1),
+                          i = the byte's index in the block: every byte of the output counts in one of them
+      deferred_groups.npy float64: the first 2^20 indices of the families left for the general path; written only when there are any
+                          (`simulate`-shaped input has none: their number is counters[2])"""
+    import numpy as np
+    import torch
+    from fgumi_amd._lib import hip_memcpy_d2h
+    os.makedirs(directory, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
+
+    n = int(out.data_len)
+    data = out.as_tensor()                      # uint8 view of the records in HBM (valid until the caller's next call)
+    save("counters", np.array([out.count, n, out.n_deferred] + list(stats), dtype=np.float64))
+    if n:
+        offsets, w = dump_window_offsets(n)
+        idx = torch.as_tensor(offsets, device=data.device)[:, None] + torch.arange(w, device=data.device)
+        save("record_windows", data[idx].to(torch.float32).cpu().numpy())
+        save("window_offsets", offsets.astype(np.float64))
+        weight = torch.arange(DUMP_BLOCK_BYTES, device=data.device, dtype=torch.int64) % 251 + 1
+        sums = []
+        for lo in range(0, n, 16 * DUMP_BLOCK_BYTES):
+            x = data[lo:lo + 16 * DUMP_BLOCK_BYTES].to(torch.int64)
+            x = torch.cat([x, x.new_zeros(-x.numel() % DUMP_BLOCK_BYTES)]).view(-1, DUMP_BLOCK_BYTES)
+            sums.append(torch.stack([x.sum(1), (x * weight).sum(1)], 1))
+        save("block_sums", torch.cat(sums).cpu().numpy().astype(np.float64))
+    k = min(int(out.n_deferred), DUMP_MAX_DEFERRED)
+    if k:
+        save("deferred_groups", np.frombuffer(hip_memcpy_d2h(out.deferred_ptr, 4 * k), dtype=np.uint32).astype(np.float64))
 
 
 def cpu_model():
@@ -283,14 +338,19 @@ def main():
                     help="simplex only: long-tail family sizes in [depth, depth-max] pairs, count ~ size^-1.5 (BASELINE configs[3] shape: --depth 2 --depth-max 50)")
     ap.add_argument("--cpu-sample-families", type=int, default=320000, help="families of the multi-thread CPU leg (320000 x 16 = 5.12 M reads at depth 8)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--end-to-end-families", type=int, default=1000000, help="N=1, simplex: families of the file -> file leg (`end_to_end` in the line); 0 skips it")
+    ap.add_argument("--end-to-end-families", type=int, default=1000000, help="N=1, simplex, --full: families of the file -> file leg (`end_to_end` in the line); 0 skips it")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
-    ap.add_argument("--no-strong-block", action="store_true", help="weak runs also time the strong-scaling reading (`strong_scaling` in the line); this skips it")
-    ap.add_argument("--no-share-block", action="store_true", help="N=1: skip the `share_of_8` block (one rank's share of an 8-way strong-scaling run, timed on this GPU)")
+    ap.add_argument("--no-strong-block", action="store_true", help="--full weak runs also time the strong-scaling reading (`strong_scaling` in the line); this skips it")
+    ap.add_argument("--no-share-block", action="store_true", help="N=1 --full: skip the `share_of_8` block (one rank's share of an 8-way strong-scaling run, timed on this GPU)")
     ap.add_argument("--gather-timeout", type=float, default=240.0, help="N>1: seconds the gather loops (run last) may take before the line is printed without them")
     ap.add_argument("--reassemble", choices=["auto", "none", "root"], default="auto",
                     help="root: a second timed loop also gathers the shard payloads to rank 0 in rank (= input) order over RCCL, reported beside `value`; "
-                         "auto = none")
+                         "auto = root beyond one rank with --full, none otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: strong_scaling, share_of_8, end_to_end, cpu_baseline and (N>1) the gather to rank 0; "
+                         "the --no-* options above switch single legs of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, < 64 MB; see dump_outputs)")
     args = ap.parse_args()
     duplex, codec = args.caller == "duplex", args.caller == "codec"
     if args.families is None:
@@ -315,10 +375,10 @@ def main():
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(test_backend or "nccl")
-    # `auto`: with more than one rank the single-writer gather (sizes all_gather + one batch_isend_irecv group into rank 0) is timed in
+    # `auto` with --full: with more than one rank the single-writer gather (sizes all_gather + one batch_isend_irecv group into rank 0) is timed in
     # a SECOND loop and reported beside `value` (value_with_reassembly_on_root / gather_GBs_into_root), never instead of it; a failure of that
     # loop is reported in `reassemble_error` and costs nothing else of the line.  One rank: nothing to gather.
-    reassemble = args.reassemble if args.reassemble != "auto" else ("root" if world > 1 else "none")
+    reassemble = args.reassemble if args.reassemble != "auto" else ("root" if (world > 1 and args.full) else "none")
 
     from fgumi_amd import (CodecConsensusCaller, CodecConsensusOptions, DuplexConsensusCaller, VanillaUmiConsensusCaller,
                            VanillaUmiConsensusOptions, simulated_family_bytes)
@@ -378,13 +438,15 @@ def main():
         dt = max_over_ranks(time.perf_counter() - t0, coll_dev)                            # MAX over ranks
         return dt, out, k_family_ms, k_emit_ms, k_total_ms, gathered
 
-    def measure(scaling, steps, warmup):
+    def measure(scaling, steps, warmup, dump_dir=None):
         """`warmup` untimed + `steps` timed passes over one workload (barrier + synchronize on both sides, MAX over ranks)."""
         dg, fam, shard_bytes = workload(scaling)
         out = None
         for _ in range(warmup):
             out = caller.process_batch_device(dg)
         dt, out, k_family_ms, k_emit_ms, k_total_ms, _ = timed_loop(dg, steps, False)       # the K timed steps: `value`
+        if dump_dir:
+            dump_outputs(dump_dir, out, caller.last_stats_array, f"rank{rank}_" if world > 1 else "")
         per_rank = gather_sizes([out.data_len, out.count, dg.n_rec, out.n_deferred, fam, shard_bytes,
                                  int(round(k_family_ms / steps * 1e3)), int(round(k_emit_ms / steps * 1e3))], coll_dev)   # rank (= input) order
         # the batch counters (ConsensusCallingStats / RejectionReason order, then the overlap CorrectionStats) summed over the ranks
@@ -456,15 +518,15 @@ def main():
                        "ms_per_step = the MEDIAN of the timed steps, each ended by a device synchronize (mean and max beside it)")
         return res
 
-    M = measure(args.scaling, args.steps, args.warmup)
+    M = measure(args.scaling, args.steps, args.warmup, args.dump_outputs)
     dt, k_family_ms, k_emit_ms, k_total_ms = M["dt"], M["k_family_ms"], M["k_emit_ms"], M["k_total_ms"]
     dt_gather, gathered_bytes, per_rank, counters, fam = M["dt_gather"], M["gathered_bytes"], M["per_rank"], M["counters"], M["fam"]
     total_bytes, total_cons, total_raw, total_def = [int(v) for v in per_rank[:, :4].sum(0).tolist()]
-    # The other reading of the metric, in the SAME invocation (the driver runs `bench.py --gpus N` once per N): north_star's target is
+    # --full: the other reading of the metric, in the SAME invocation (`bench.py --gpus N --full` once per N): north_star's target is
     # strong scaling — ONE stream of `families` molecules cut over the ranks.  The weak line's step IS the N=1 workload on every GPU
     # (`families` per GPU), so its step time is this run's own N=1 reference: speedup_vs_n1 = weak ms_per_step / strong ms_per_step.
     S = None
-    if args.scaling == "weak" and not args.no_strong_block:
+    if args.full and args.scaling == "weak" and not args.no_strong_block:
         S = measure("strong", max(1, min(args.steps, 10)), 1)
 
     if rank == 0:
@@ -559,17 +621,17 @@ def main():
                 "value_with_reassembly_on_root": (s_raw * s_steps / S["dt_gather"]) if S["dt_gather"] else None,
             }
         # (the GPU legs back to back, before the host-side ones: the share step is latency bound and the first to feel a busy host)
-        if world == 1 and plain and not args.no_share_block and not args.no_cpu_baseline and args.families >= 8:     # (profiling runs — --no-cpu-baseline — time the headline workload alone)
+        if args.full and world == 1 and plain and not args.no_share_block and not args.no_cpu_baseline and args.families >= 8:     # (profiling runs — --no-cpu-baseline — time the headline workload alone)
             try:
                 line["share_of_8"] = share_of_8()
             except Exception as ex:
                 line["share_of_8"] = {"error": str(ex)[:300]}
-        if world == 1 and plain and args.end_to_end_families > 0 and not args.no_cpu_baseline:     # (the two extra legs go together: profiling runs switch both off)
+        if args.full and world == 1 and plain and args.end_to_end_families > 0 and not args.no_cpu_baseline:     # (the two extra legs go together: profiling runs switch both off)
             try:
                 line["end_to_end"] = end_to_end(caller, min(args.end_to_end_families, fam), args.depth, L, os.environ.get("FGX_BENCH_TMP", "/tmp/fgx_bench_e2e"))
             except Exception as ex:                      # (a full /tmp or a read-only file system must not cost the line)
                 line["end_to_end"] = {"error": str(ex)[:300]}
-        if not args.no_cpu_baseline and world == 1 and not args.depth_max:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.depth_max:
             # threads = the CPUs the container may really use (cgroup quota): oversubscribing a throttled cgroup only adds queueing
             T = min(os.cpu_count() or 1, cgroup_cpu_quota() or 1 << 30)
             line["cpu_baseline"] = cpu_baseline(min(fam, args.cpu_sample_families), args.depth, L, T, duplex, codec)

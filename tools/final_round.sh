@@ -18,7 +18,7 @@ done
 python $R/tools/pmc_parse.py $OUT/pmc 3 > $OUT/pmc_5M_families.json && cp $OUT/pmc_5M_families.json $R/profiles/${TAG}_pmc_5M_families.json
 rm -rf $OUT/pmc
 cd $R
-timeout 400 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench_line.json
+timeout 400 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench_line.json
 cd /tmp
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o simplex -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/stats.log 2>&1
 rm -rf $OUT/*_agent_info.csv $OUT/*kernel_trace.csv

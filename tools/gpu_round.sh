@@ -4,7 +4,7 @@
 TAG=$1; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; cd $R
 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider -rfEs --durations=12 > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log
 grep -E "passed|failed|^FAILED|^ERROR" $OUT/pytest.log | tail -25
-timeout 400 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-700 $OUT/bench_line.json
+timeout 400 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-700 $OUT/bench_line.json
 python - $OUT/bench_line.json <<'PY'
 import json, sys
 try:

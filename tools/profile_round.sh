@@ -21,7 +21,7 @@ python $R/tools/pmc_parse.py $OUT/pmc 3 > $OUT/pmc_5M_families.json
 cp $OUT/pmc_5M_families.json $R/profiles/${TAG}_pmc_5M_families.json
 rm -rf $OUT/pmc
 cd $R
-python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench_line.json
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench_line.json
 line() { local name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline > $OUT/$name.log 2>&1; grep '^{' $OUT/$name.log | tail -1 > $OUT/${name}_bench_line.json
   python -c "import sys,json; d=json.load(open('$OUT/${name}_bench_line.json')); print('$name', 'k_family_ms=%.2f k_emit_ms=%.2f ms_step=%.2f reads/s=%.4g'%(d['roofline']['kernel_ms'], d['roofline']['k_emit_ms'], d['ms_per_step'], d['value']))"; }
 line depth3 --families 5000000 --depth 3 --steps 5 --warmup 1
