@@ -537,7 +537,9 @@ class DuplexConsensusCaller(_HandleCaller):
 
     def set_reference(self, reference, ref_names: Sequence[str], methylation_mode: Optional[int] = None):
         """`DuplexConsensusCaller::set_reference(reference, ref_names, methylation_mode)` (duplex_caller.rs:524-536): the mode
-        goes to the single-strand caller's options (a new engine handle when it differs from the constructor's)."""
+        goes to the single-strand caller's options (a new engine handle when it differs from the constructor's).  With the mode
+        and a reference set, `process_batch_device`, `process_batch` and `run_bam` decide molecules of single-block reads in the
+        device-resident pipeline (am/au/at, bm/bu/bt, MM/ML/cu/ct in the records); the rest is deferred to the general path."""
         if methylation_mode is not None and int(methylation_mode) != self._opts.methylation_mode:
             self.close()
             self._opts.methylation_mode = int(methylation_mode)

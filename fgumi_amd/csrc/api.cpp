@@ -621,10 +621,11 @@ static int hybrid_after_upload(fgx_caller* c, general_fn general, const uint8_t*
                                const uint32_t* rec_len, uint32_t n_rec, const uint32_t* grp_first, uint32_t n_grp, fgx_output* out,
                                uint8_t* dst, uint64_t dst_cap);
 
-// The methylation-aware mode in the device-resident pipeline (round 4; FGX_METH_DEVICE=0 opts out): simplex caller, a reference handed over,
-// no --trim, no --rejects.  Everything else of the mode stays on the general path.
+// The methylation-aware mode in the device-resident pipeline (FGX_METH_DEVICE=0 opts out): simplex caller (the streaming kernels of simplex_deep.inc) or
+// duplex caller (k_family_wave<1, 1>, duplex_meth.inc), a reference handed over, no --trim, no --rejects.  Everything else of the mode stays on the
+// general path.
 static bool meth_device_enabled(const fgx_caller* c) {
-  if (c->opt.caller_kind != FGX_CALLER_SIMPLEX || c->opt.trim || c->opt.track_rejects || !c->genome) return false;
+  if ((c->opt.caller_kind != FGX_CALLER_SIMPLEX && c->opt.caller_kind != FGX_CALLER_DUPLEX) || c->opt.trim || c->opt.track_rejects || !c->genome) return false;
   const char* e = getenv("FGX_METH_DEVICE");
   return !(e && e[0] == '0');
 }
@@ -853,7 +854,10 @@ static int hybrid_after_upload(fgx_caller* c, general_fn general, const uint8_t*
   cp.used.assign(def.size(), 0);
   c->last_canon_molecules = 0;
   c->last_deferred_groups = (uint64_t)def.size();
-  if ((c->opt.caller_kind == FGX_CALLER_DUPLEX && duplex_canon_enabled()) || (c->opt.caller_kind == FGX_CALLER_CODEC && codec_canon_enabled()))
+  // (not in the methylation-aware mode: the canonical form moves and re-lengths the reads, and an annotation is tied to its anchor's place on the reference —
+  // what the device pass defers there is the general path's)
+  if (c->opt.methylation_mode == FGX_METHYLATION_DISABLED &&
+      ((c->opt.caller_kind == FGX_CALLER_DUPLEX && duplex_canon_enabled()) || (c->opt.caller_kind == FGX_CALLER_CODEC && codec_canon_enabled())))
     canon_second_pass(c, records, rec_off, rec_len, grp_first, def, cp);
   std::vector<uint64_t> d_off;
   std::vector<uint32_t> d_len, d_grp(1, 0);
@@ -1030,8 +1034,8 @@ int fgx_process_batch_device(fgx_caller* c, const void* d_records, uint64_t reco
     const bool dev_rejects = c->opt.track_rejects && c->opt.caller_kind == FGX_CALLER_SIMPLEX && rejects_device_enabled();
     const bool strand_rejects = c->opt.track_rejects && (c->opt.caller_kind == FGX_CALLER_DUPLEX || c->opt.caller_kind == FGX_CALLER_CODEC) && rejects_device_enabled();
     if (c->opt.track_rejects && !dev_rejects && !strand_rejects) { c->err = "fgx_process_batch_device: --rejects needs the host path (fgx_process_batch)"; return 1; }
-    // methylation-aware mode: the simplex caller without --trim runs on the streaming kernels (simplex_deep.inc); FGX_METH_DEVICE=0, duplex or
-    // --trim: the host entry (general path)
+    // methylation-aware mode: the simplex caller (streaming kernels, simplex_deep.inc) and the duplex caller (k_family_wave<1, 1>) without --trim run here;
+    // FGX_METH_DEVICE=0, no reference or --trim: the host entry (general path)
     if (c->opt.methylation_mode != FGX_METHYLATION_DISABLED && !meth_device_enabled(c)) { c->err = "fgx_process_batch_device: the methylation-aware mode of this caller needs the host entry (fgx_process_batch)"; return 1; }
     if (!c->fast) c->fast = new FastState();
     c->fast->has_last = false;   // set again only when this batch succeeds
@@ -1051,7 +1055,7 @@ int fgx_process_batch_device(fgx_caller* c, const void* d_records, uint64_t reco
     c->last_deferred_groups = fr.n_deferred; c->last_canon_molecules = 0;
     c->last_group_off = fr.d_out_off; c->last_group_stride = 3;
     uint32_t left_deferred = fr.n_deferred;      // (after the canonical second pass, when it runs)
-    if (fr.n_deferred > 0 && canon_resident_enabled(c->opt.caller_kind)) {
+    if (fr.n_deferred > 0 && c->opt.methylation_mode == FGX_METHYLATION_DISABLED && canon_resident_enabled(c->opt.caller_kind)) {   // (never in the methylation-aware mode: see hybrid_after_upload)
       ResidentOut ro;
       if (canon_resident_pass(c, (const uint8_t*)d_records, (const uint64_t*)d_rec_off, (const uint32_t*)d_rec_len, (const uint32_t*)d_grp_first, n_grp, fr, &ro)) {
         c->fast->has_last = false;                  // (the slot tables of `last` describe one pass only: fgx_filter_last_output_device has to be given the records)

@@ -32,7 +32,13 @@ struct DuplexDesc {         // one duplex consensus record (slot 3g+1 = R1, 3g+2
   uint8_t mi_len, cb_len, rx_len, type;
   uint8_t has_cb, has_rx, valid, has_ba;
   char rx[FAST_RX_CAP];
+  uint8_t meth;             // methylation-aware mode (k_family_wave<1, 1>; in what was padding): bit 0 the AB-side strand's call was annotated, bit 1 the BA-side
+                            // strand's, bit 2 a lone strand passed through is the BA one (is_ba_only: its tags are bm / bu / bt and its MM strand is G-m)
 };
+static_assert(sizeof(DuplexDesc) == 96, "DuplexDesc: the methylation byte lies in the padding");
+// methylation-aware mode, duplex: what k_duplex_meth_sizes found for a record — the bytes of the standard record (the methylation tags follow them) and per
+// MM string (0 the AB-side strand's am / bm, 1 the BA-side strand's bm, 2 the duplex MM) its entries and the characters of its entries
+struct DuplexMethSlot { uint32_t std_size, n_hit[3], mm_len[3], _pad; };
 
 struct CodecDesc {          // one CODEC consensus record (slot 3g+1), written by k_family_wave<2>, consumed by k_emit_codec
   uint64_t s1_off, s2_off;  // R1-strand and R2-strand single-strand column segments (read orientation)
@@ -159,7 +165,7 @@ struct FastParams {
   uint32_t meth_mode, n_ref;
   const uint8_t* genome; const uint64_t* contig_off; const uint64_t* contig_len;
   uint8_t* meth_flag; uint16_t* meth_u; uint16_t* meth_t;
-  // duplex (k_family_wave<1>)
+  // duplex (k_family_wave<1>; with the methylation-aware mode k_family_wave<1, 1>, which fills meth_flag / meth_u / meth_t per column of the four read sets)
   uint32_t dmin_total, dmin_xy, dmin_yx; int64_t dmax_reads;
   uint32_t* col_obs;               // per column: observation counts of A,C,G,T, one byte each
   DuplexDesc* dends;
@@ -183,6 +189,7 @@ struct DuplexEmitParams {
   const char* prefix; uint32_t prefix_len; const char* rg; uint32_t rg_len;
   uint8_t per_base_tags; char cell0, cell1;
   uint32_t* n_slow;                // k_count_slow_duplex counts the valid records the fast writer leaves to the per-field kernel here (0: that kernel is not launched at all)
+  const uint8_t* meth_flag;        // methylation-aware mode (the <1> builds of the writers): per column, the reference shows a cytosine of the strand's call
 };
 
 struct CodecEmitParams {

@@ -1104,7 +1104,9 @@ inline void build_fw_image(FwLds& L, const ConsensusTables& t) {
   for (uint32_t i = 0; i < 256; i++) { const int fx = bam::tag_fixed_size((uint8_t)i); L.tagcls[i] = (uint8_t)(fx ? fx : i == 'Z' ? 8 : i == 'H' ? 16 : i == 'B' ? 32 : 0); }
 }
 
-template <int MODE>
+// METH 1 (duplex only): the methylation-aware mode — per read set the anchor read's place on the reference, the unconverted / converted counts of every
+// column and converted bases read as unconverted ones before they are observed (see 6D); molecules with a record of more than one CIGAR op are deferred.
+template <int MODE, int METH = 0>
 #ifndef FGX_WAVE_OCC_DUPLEX
 #define FGX_WAVE_OCC_DUPLEX 4   /* the duplex branch holds four column sets' worth of state beside the record lanes: at 5 waves per SIMD (96 VGPRs) its
                                    member loop spilled */
@@ -1233,6 +1235,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       seq_lo = lo + (uint32_t)seq_off; qual_lo = lo + (uint32_t)qual_off;
       excluded = (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) != 0;
       if (MODE == 1 && excluded) bad = true;   // the duplex caller has no secondary/supplementary filter: general path
+      if (METH != 0 && n_cig != 1) bad = true;   // methylation-aware mode: column p of a read set lies at the anchor's pos + p (or its end - p) only when the read is one aligned block
       if (MODE == 2 && (excluded || !(flags & bam::F_PAIRED))) bad = true;   // CODEC: fragments / non-primary records take the general path
       // CIGAR: one aligned block of M/=/X ops, optionally between soft / hard clips (what an aligner gives a read without
       // indels).  Such reads all simplify to (M, length) for the alignment filter; clips only shift query offsets.
@@ -1870,12 +1873,43 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   KC.cap_threshold = uniform_f64(sT.cap_threshold); KC.half_cerr_at_cap = uniform_f64(sT.half_cerr_at_cap);
   uint32_t dm_tr[4] = {0, 0, 0, 0}, dm_fu[4] = {0, 0, 0, 0};     // max depth over the paired (truncated) span / the whole strand
   bool odd_base = false;
+  bool ann_set[4] = {false, false, false, false};                // methylation-aware mode: the set's call was annotated
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const unsigned long long members = em[k];
     if (!members) continue;
     const uint32_t mc = (uint32_t)__popcll(members);
     const uint32_t plen = (k == 0 || k == 3) ? plen1 : plen2;
+    // Methylation-aware mode (annotate_and_normalize, vanilla_caller.rs:781-860; methylation.rs:193-242): the call's anchor is the LAST longest
+    // source read of the set (max_by_key; file order = lane order), taken over all its reads — a cap that bites is deferred above.  Every read here
+    // is one aligned block, so column p lies at the anchor's pos + p (forward) or at its last aligned base - p (reverse: the columns run in read
+    // orientation).  The strand of the call is is_top_strand of the anchor's flags (methylation.rs:392-398): C / T against a reference C, else G / A
+    // against a reference G.  No annotation (no tags from this call, nothing normalised) when the anchor names no contig of the genome handed over.
+    bool ann = false, a_rev = false;
+    long long a_ref0 = 0;
+    unsigned long long g_off = 0, g_len = 0;
+    uint32_t tcode = 0, vcode = 0, target = 0;                     // unconverted / converted read base as 4-bit codes in consensus orientation; the reference base
+    if constexpr (METH != 0) {
+      const unsigned long long lm = members & __ballot(final_len == elen[k]);
+      const uint32_t an = 63u - (uint32_t)__clzll((long long)lm);
+      const uint32_t a_flags = rlane(flags, an), a_lseq = rlane(l_seq, an);
+      const int32_t a_pos = (int32_t)rlane((uint32_t)pos, an), a_ref = (int32_t)rlane((uint32_t)ref_id, an);
+      a_rev = (a_flags & bam::F_REVERSE) != 0;
+      const bool a_top = a_rev == ((a_flags & bam::F_LAST) != 0);
+      tcode = a_top ? 2u : 4u; vcode = a_top ? 8u : 1u; target = a_top ? (uint32_t)'C' : (uint32_t)'G';
+      ann = a_ref >= 0 && a_pos >= 0 && (uint32_t)a_ref < P.n_ref;
+      a_ref0 = a_rev ? (long long)a_pos + (long long)a_lseq - 1 : (long long)a_pos;
+      if (ann) { g_off = uniform_u64(P.contig_off[a_ref]); g_len = uniform_u64(P.contig_len[a_ref]); }
+      ann_set[k] = ann;
+    }
+    auto ref_is_c = [&](uint32_t p) -> bool {                      // the reference shows a cytosine of the call's strand under column p
+      if (!ann) return false;
+      const long long rp = a_rev ? a_ref0 - (long long)p : a_ref0 + (long long)p;
+      if (rp < 0 || (unsigned long long)rp >= g_len) return false;
+      uint32_t rb = P.genome[g_off + (unsigned long long)rp];
+      if (rb >= 'a' && rb <= 'z') rb -= 32;
+      return rb == target;
+    };
     // A REGULAR set — every member on one strand (reverse: one read length), untrimmed: the usual set — takes k_simplex_wave2's column
     // step (chain_observe.inc: ~20 vector instructions per observation instead of ~50; the lane's index into a member is the same for
     // every member, a member's final length is a scalar lane mask, the codes stay as stored and the chains' bases are complemented once
@@ -1905,13 +1939,23 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         double s1 = 0.0, c1 = 0.0, sR = 0.0, cR = 0.0, s2, c2, s3, c3;
         FGX_UNDEF4(s2, c2, s3, c3);   // (chains 2 / 3: written when opened)
         uint32_t allow = incol ? 0x116u : 0u, b1 = 0, b2 = 0, b3 = 0, n1 = 0, n2 = 0, n3 = 0, nR = 0;
+        // methylation-aware mode: the codes stay as stored here, so a reverse set's unconverted / converted bases are the complements
+        bool is_c = false;
+        uint32_t mu = 0, mt = 0, tcs = 0, vcs = 0;
+        if constexpr (METH != 0) {
+          is_c = incol && ref_is_c(p);
+          tcs = set_rev ? __builtin_bitreverse32(tcode) >> 28 : tcode; vcs = set_rev ? __builtin_bitreverse32(vcode) >> 28 : vcode;
+        }
         for (unsigned long long m = members; m;) {
           const uint32_t r = (uint32_t)__builtin_ctzll(m);
           m &= m - 1;
           const uint32_t x0 = rlane(d0, r), x1 = rlane(d1, r);
           const bool in = __builtin_amdgcn_inverse_ballot_w64(fw_lanes_below(x1 >> 16, (uint32_t)__builtin_amdgcn_readfirstlane((int)p0)));   // inside this member's final length
           const uint32_t q = W[iq + (x0 >> 16)];
-          const uint32_t c = __builtin_amdgcn_ubfe((uint32_t)W[is + (x0 & 0xFFFF)], ish, 4u);
+          uint32_t c = __builtin_amdgcn_ubfe((uint32_t)W[is + (x0 & 0xFFFF)], ish, 4u);
+          if constexpr (METH != 0) {   // counted, and the converted base read as the unconverted one, BEFORE it is observed (a masked base is an N: not counted)
+            if (is_c && in && q >= min_bq) { if (c == tcs) mu++; else if (c == vcs) { mt++; c = tcs; } }
+          }
           W2_OBSERVE(0, in, q, c, *(const double2*)(pairs + (((q) < 93u ? (q) : 93u) << 4)));
         }
         if (allow != 0) b1 = (uint32_t)__builtin_ctz(allow);
@@ -1940,6 +1984,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
             P.col_code[o] = ob; P.col_qual[o] = oq; P.col_err[o] = (uint16_t)err;
           }
           P.col_obs[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24);
+          if constexpr (METH != 0) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; }
           dm_fu[k] = depth > dm_fu[k] ? depth : dm_fu[k];
           if (p < plen) dm_tr[k] = depth > dm_tr[k] ? depth : dm_tr[k];
         }
@@ -1955,9 +2000,13 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     for (uint32_t p = lane; p < elen[k]; p += 64) {
       const uint64_t o = col_base + eoff[k] + p;
       uint32_t depth, obs[4];
+      bool is_c = false;
+      uint32_t mu = 0, mt = 0;
+      if constexpr (METH != 0) is_c = ref_is_c(p);
       if (mc == 1) {   // single-read consensus: LUT keyed by the unclamped quality (vanilla_caller.rs:1677-1708)
         uint32_t code, q;
         view(one_seq, one_qual, one_lseq, (one_flags & bam::F_REVERSE) != 0, one_trim, p, &code, &q);
+        if constexpr (METH != 0) { if (is_c) { if (code == tcode) mu = 1; else if (code == vcode) { mt = 1; code = tcode; } } }   // (`view` gives the masked base as N)
         const uint8_t adj = q < 94 ? T->single_input_quals[q] : 0;
         const bool low = adj < FGX_MIN_PHRED;
         P.col_code[o] = low ? (uint8_t)15 : (uint8_t)code; P.col_qual[o] = low ? (uint8_t)FGX_MIN_PHRED : adj; P.col_err[o] = 0;
@@ -1976,8 +2025,9 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
           const uint32_t bb = W[(x0 & 0xFFFF) + (idx >> 1)];
           const uint32_t c = (bb >> ((~idx & 1) << 2)) & 15;
           const uint32_t q = W[(x0 >> 16) + idx];
-          const uint32_t co = rv ? __builtin_bitreverse32(c) >> 28 : c;     // read orientation: complement = bit reversal of the code
+          uint32_t co = rv ? __builtin_bitreverse32(c) >> 28 : c;           // read orientation: complement = bit reversal of the code
           const bool masked = p < (x2 & 0xFFFF) && q < min_bq;
+          if constexpr (METH != 0) { if (is_c && valid && !masked) { if (co == tcode) mu++; else if (co == vcode) { mt++; co = tcode; } } }
           valid = valid && __popc(co) == 1 && !masked;                      // only the one-hot codes A C G T are observations
           const uint32_t qq = q < FGX_MAX_PHRED ? q : FGX_MAX_PHRED;
           const double2 pr = *(const double2*)&sPair[qq][0];
@@ -2000,6 +2050,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         }
       }
       P.col_obs[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24);
+      if constexpr (METH != 0) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; }
       dm_fu[k] = depth > dm_fu[k] ? depth : dm_fu[k];
       if (p < plen) dm_tr[k] = depth > dm_tr[k] ? depth : dm_tr[k];
     }
@@ -2129,6 +2180,10 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         D->mi_off = (uint16_t)(fp_mi_lo - fp_lo); D->mi_len = (uint8_t)fp_mi_len;
         D->has_cb = fc_has_cb ? 1 : 0; D->cb_off = (uint16_t)(fc_cb_lo - fc_lo); D->cb_len = (uint8_t)fc_cb_len;
         D->has_rx = cnt > 0; D->rx_len = (uint8_t)ulen; D->type = (uint8_t)(1 + t); D->has_ba = O.has_ba ? 1 : 0;
+        if constexpr (METH != 0) {   // which strands carry an annotation; a lone strand passed through keeps the BA side's tag names (duplex_caller.rs:1338-1398)
+          auto ann_of = [&](uint32_t kk) { return kk == 0 ? ann_set[0] : kk == 1 ? ann_set[1] : kk == 2 ? ann_set[2] : ann_set[3]; };
+          D->meth = (uint8_t)((ann_of(O.sa) ? 1u : 0u) | ((O.has_ba && ann_of(O.sb)) ? 2u : 0u) | ((!O.has_ba && O.sa >= 2) ? 4u : 0u));
+        }
         const uint32_t nm = P.prefix_len + 1 + fp_mi_len;
         const uint32_t per_strand = P.per_base_tags ? 2 * (3 + L + 1) + 2 * (8 + 2 * L) : 0;     // ac/aq strings + ad/ae arrays
         // every int tag holds a depth <= 128 here (<= 64 records per wavefront): 4 bytes each
@@ -3173,7 +3228,25 @@ __device__ __forceinline__ uint32_t obs_of_code(uint32_t o, uint32_t code) {   /
   return code == 1 ? (o & 0xFF) : code == 2 ? ((o >> 8) & 0xFF) : code == 4 ? ((o >> 16) & 0xFF) : code == 8 ? (o >> 24) : 0u;
 }
 __device__ __forceinline__ uint32_t cap_q(int32_t v) { return v < 2 ? 2u : v > 93 ? 93u : (uint32_t)v; }
+// The raw duplex call of one position from the two single-strand calls (duplex_consensus, duplex_caller.rs:979-1020), bases as 4-bit codes.
+// METH 1, the methylation-aware mode's conversion-artifact rule (:988-1005): a C / T or G / A disagreement at a column that either strand's
+// annotation flags as a reference cytosine (`ref_c`) is a conversion event — the unconverted base, the qualities added, and no error counted
+// (`artifact`).  The record writers and the methylation tag kernels (MM is built from the duplex bases) share it.
+template <int METH>
+__device__ __forceinline__ void duplex_combine(uint32_t ca, uint32_t qa, uint32_t cb, uint32_t qb, bool ref_c, uint32_t& rb, uint32_t& rq, bool& artifact) {
+  artifact = false;
+  if constexpr (METH != 0) {
+    const uint32_t both = ca | cb;                                    // {C, T} = 2 | 8, {G, A} = 4 | 1 (an N, 15, makes neither)
+    artifact = ref_c && ca != cb && (both == 10u || both == 5u);
+    if (artifact) { rb = both == 10u ? 2u : 4u; rq = cap_q((int32_t)qa + (int32_t)qb); return; }
+  }
+  if (ca == cb) { rb = ca; rq = cap_q((int32_t)qa + (int32_t)qb); }
+  else if (qa > qb) { rb = ca; rq = cap_q((int32_t)qa - (int32_t)qb); }
+  else if (qb > qa) { rb = cb; rq = cap_q((int32_t)qb - (int32_t)qa); }
+  else { rb = ca; rq = FGX_MIN_PHRED; }
+}
 
+template <int METH>     // 1: the methylation-aware mode (the conversion-artifact rule in the strand combine)
 __global__ __launch_bounds__(256) void k_emit_duplex(DuplexEmitParams P) {
   const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(P.slot0 + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6)));
   const uint32_t lane = threadIdx.x & 63;
@@ -3198,15 +3271,14 @@ __global__ __launch_bounds__(256) void k_emit_duplex(DuplexEmitParams P) {
     const uint32_t ob = P.col_obs[b_off + i];
     c.cb = P.col_code[b_off + i]; c.qb = P.col_qual[b_off + i]; c.eb = P.col_err[b_off + i]; c.db = obs_sum(ob);
     uint32_t rb, rq;
-    if (c.ca == c.cb) { rb = c.ca; rq = cap_q((int32_t)c.qa + (int32_t)c.qb); }
-    else if (c.qa > c.qb) { rb = c.ca; rq = cap_q((int32_t)c.qa - (int32_t)c.qb); }
-    else if (c.qb > c.qa) { rb = c.cb; rq = cap_q((int32_t)c.qb - (int32_t)c.qa); }
-    else { rb = c.ca; rq = FGX_MIN_PHRED; }
+    bool artifact, ref_c = false;
+    if constexpr (METH != 0) ref_c = (P.meth_flag[a_off + i] | P.meth_flag[b_off + i]) != 0;
+    duplex_combine<METH>(c.ca, c.qa, c.cb, c.qb, ref_c, rb, rq, artifact);
     const bool nocall = c.ca == 15 || c.cb == 15 || rq == FGX_MIN_PHRED;
     c.oc = nocall ? 15u : rb; c.oq = nocall ? (uint32_t)FGX_MIN_PHRED : rq;
-    // errors: source reads of both strands that disagree with the raw duplex base (N never counts)
+    // errors: source reads of both strands that disagree with the raw duplex base (N never counts; a conversion event is no error)
     const uint32_t agree = obs_of_code(oa, rb) + obs_of_code(ob, rb);
-    c.oe = rb == 15 ? 0u : (c.da + c.db) - agree;
+    c.oe = (rb == 15 || artifact) ? 0u : (c.da + c.db) - agree;
     return c;
   };
   // ---- reductions for aD aM aE / bD bM bE / cD cM cE -------------------------------------------------------------------------
@@ -3613,6 +3685,7 @@ __global__ __launch_bounds__(256) void k_count_slow_codec(const CodecDesc* __res
   const unsigned long long m = __ballot(slow);
   if (m && (threadIdx.x & 63) == 0) atomicAdd(n_slow, (uint32_t)__popcll(m));
 }
+template <int METH>     // 1: the methylation-aware mode (the conversion-artifact rule in the strand combine)
 __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
   const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(P.slot0 + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6)));
   const uint32_t lane = threadIdx.x & 63;
@@ -3629,6 +3702,7 @@ __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
   const uint32_t flag = bam::F_UNMAPPED | bam::F_PAIRED | bam::F_MATE_UNMAPPED | (D.type == 1 ? bam::F_FIRST : bam::F_LAST);
   // ---- every load of the record (indices clamped into the record's own segments, so unconditional) -----------------------
   uint32_t ca[DUP_SLOTS][2], qa[DUP_SLOTS][2], ea[DUP_SLOTS][2], oa[DUP_SLOTS][2], cb[DUP_SLOTS][2], qb[DUP_SLOTS][2], eb[DUP_SLOTS][2], ob[DUP_SLOTS][2];
+  uint32_t rc[DUP_SLOTS];           // methylation-aware mode: either strand flags a reference cytosine, a byte per position of the pair
 #pragma unroll
   for (uint32_t t = 0; t < DUP_SLOTS; t++) {
     // (round 6) a lane's two neighbouring positions with ONE load per array and strand (2 + 2 + 4 + 8 bytes) instead of one per position: 16 vector memory
@@ -3643,6 +3717,8 @@ __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
     };
     ld2(a_off + pc, ca[t], qa[t], ea[t], oa[t]);
     ld2(b_off + pc, cb[t], qb[t], eb[t], ob[t]);
+    rc[t] = 0;
+    if constexpr (METH != 0) { uint16_t fa, fb; __builtin_memcpy(&fa, P.meth_flag + a_off + pc, 2); __builtin_memcpy(&fb, P.meth_flag + b_off + pc, 2); rc[t] = (uint32_t)(fa | fb); }
   }
   const uint32_t k3 = lane >= 3 ? lane - 3 : 0, ni = lane > P.prefix_len ? lane - P.prefix_len - 1 : 0;
   const uint8_t pfx = (uint8_t)P.prefix[lane < P.prefix_len ? lane : 0], nmb = first[mi_off + (ni < mi_len ? ni : mi_len)];
@@ -3659,13 +3735,11 @@ __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
         db = obs_sum(ob[t][k]); xcb = cb[t][k]; xqb = qb[t][k]; xeb = eb[t][k];
         const uint32_t xa = ca[t][k], xq = qa[t][k];
         uint32_t rb, rq;
-        if (xa == xcb) { rb = xa; rq = cap_q((int32_t)xq + (int32_t)xqb); }
-        else if (xq > xqb) { rb = xa; rq = cap_q((int32_t)xq - (int32_t)xqb); }
-        else if (xqb > xq) { rb = xcb; rq = cap_q((int32_t)xqb - (int32_t)xq); }
-        else { rb = xa; rq = FGX_MIN_PHRED; }
+        bool artifact;
+        duplex_combine<METH>(xa, xq, xcb, xqb, ((rc[t] >> (8 * k)) & 0xFFu) != 0, rb, rq, artifact);
         const bool nocall = xa == 15 || xcb == 15 || rq == FGX_MIN_PHRED;
         oc = nocall ? 15u : rb; oq = nocall ? (uint32_t)FGX_MIN_PHRED : rq;
-        oe = rb == 15 ? 0u : (da + db) - (obs_of_code(oa[t][k], rb) + obs_of_code(ob[t][k], rb));
+        oe = (rb == 15 || artifact) ? 0u : (da + db) - (obs_of_code(oa[t][k], rb) + obs_of_code(ob[t][k], rb));
       }
       w0[t][k] = ca[t][k] | (xcb << 4) | (oc << 8) | (qa[t][k] << 16) | (xqb << 24);
       w1[t][k] = da | (db << 8) | (ea[t][k] << 16) | (xeb << 24);
@@ -3853,6 +3927,7 @@ __global__ __launch_bounds__(256) void k_emit_codec_fast(CodecEmitParams P) {
 #include "simplex_seg.inc"
 #include "simplex_split.inc"
 #include "simplex_deep.inc"
+#include "duplex_meth.inc"
 
 // Upper bound on the consensus columns a batch can produce: a family yields at most three ends, each no
 // longer than its longest read, and l_seq <= (block_size - 33) * 2 / 3.
@@ -4001,6 +4076,10 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
   // family on their list, the reference lookup / counts / normalisation in k_deep_cols<1>, MM / ML / cu / ct behind the standard record
   // (k_meth_sizes, k_meth_tail); a family outside their shape is deferred to the general path, which knows the mode.
   const bool meth_dev = !duplex && !codec && !o.trim && o.methylation_mode != FGX_METHYLATION_DISABLED && c->genome != nullptr;
+  // The duplex caller in the mode (a reference set, no --trim): the wavefront kernel's <1, 1> build annotates and normalises the four read sets of a
+  // molecule in its column loops, the record writers' <1> builds apply the conversion-artifact rule, am/au/at, bm/bu/bt, MM/ML/cu/ct follow RX
+  // (duplex_meth.inc).  A caller with the mode off launches the builds it always did.
+  const bool meth_dup = duplex && !o.trim && o.methylation_mode != FGX_METHYLATION_DISABLED && c->genome != nullptr;
   last_meth_device = 0;
   const bool simplex_v2 = !duplex && !codec && !o.trim && use_v2 && !meth_dev;
   const bool seg4 = simplex_v2 && use_seg && mean_span + (16 * 8 + 64) <= seg_bytes / 4;
@@ -4101,7 +4180,10 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
     hip_check(hipMemsetAsync(d_sizes.p, 0, ((size_t)n_slots + 1) * 8, s), "memset");
   }
   d_code.reserve(col_cap + 64); d_qual.reserve(col_cap + 64); d_err.reserve(col_cap * 2 + 64);   // (+ slack: k_emit reads whole dwords)
-  if (meth_dev) { d_mflag.reserve(col_cap + 64); d_mu.reserve(col_cap * 2 + 64); d_mt.reserve(col_cap * 2 + 64); d_mslot.reserve((size_t)n_slots * sizeof(MethSlot) + 64); }
+  if (meth_dev || meth_dup) {
+    d_mflag.reserve(col_cap + 64); d_mu.reserve(col_cap * 2 + 64); d_mt.reserve(col_cap * 2 + 64);
+    d_mslot.reserve((size_t)n_slots * (meth_dup ? sizeof(DuplexMethSlot) : sizeof(MethSlot)) + 64);
+  }
   if (duplex) d_obs.reserve(col_cap * 4); else d_depth.reserve(col_cap * 2 + 64);
 
   FastParams P;
@@ -4145,7 +4227,7 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
   P.prefix_len = (uint32_t)c->prefix.size(); P.rg_len = (uint32_t)c->rg.size();
   P.ends = d_ends.as<EndDesc>(); P.rec_sizes = d_sizes.as<uint64_t>();
   P.col_code = d_code.as<uint8_t>(); P.col_qual = d_qual.as<uint8_t>(); P.col_depth = d_depth.as<uint16_t>(); P.col_err = d_err.as<uint16_t>();
-  if (meth_dev) {
+  if (meth_dev || meth_dup) {
     const GenomeRef* gr = c->genome.get();
     const uint32_t n_ref = (uint32_t)gr->off.size();
     d_mcontigs.reserve((size_t)(n_ref + 1) * 16 + 64);
@@ -4188,6 +4270,7 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
       hip_check(hipFuncSetAttribute((const void*)k_family_wave<0>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<0>: the device refused the dynamic LDS size");
       hip_check(hipFuncSetAttribute((const void*)k_family_wave<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<1>: the device refused the dynamic LDS size");
       hip_check(hipFuncSetAttribute((const void*)k_family_wave<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<2>: the device refused the dynamic LDS size");
+      hip_check(hipFuncSetAttribute((const void*)k_family_wave<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<1, 1>: the device refused the dynamic LDS size");
       lds_attr_set = true;
     }
     d_retry2.reserve((size_t)n_grp * 4);
@@ -4506,6 +4589,7 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
       const dim3 grid((n_cur + wpb - 1) / wpb), block(64 * wpb);
       const size_t lds = (size_t)wpb * stages[st];
       if (codec) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<2>), grid, block, lds, s, PS, n_cur); } while (0);
+      else if (meth_dup) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<1, 1>), grid, block, lds, s, PS, n_cur); } while (0);
       else if (duplex) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<1>), grid, block, lds, s, PS, n_cur); } while (0);
       else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<0>), grid, block, lds, s, PS, n_cur); } while (0);
       hip_check(hipGetLastError(), "k_family_wave launch");
@@ -4514,6 +4598,7 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
       FGX_SYNC(s);
       cur_list = lists[out_list]; n_cur = PS.retry ? n_next : 0; out_list ^= 1;
     }
+    if (meth_dup) last_meth_device = n_grp;
     uint32_t n_big = 0;
     if (!duplex && !codec) {
       if (split_counts_seen && last_routed == 0) n_big = h_big_seen;   // (no kernel after the split stages has run: what their last synchronisation read is final)
@@ -4653,6 +4738,10 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
     do { last_launches++; hipLaunchKernelGGL(k_meth_sizes, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<MethSlot>()); } while (0);
     hip_check(hipGetLastError(), "k_meth_sizes launch");
   }
+  if (meth_dup) {
+    do { last_launches++; hipLaunchKernelGGL(k_duplex_meth_sizes, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<DuplexMethSlot>()); } while (0);
+    hip_check(hipGetLastError(), "k_duplex_meth_sizes launch");
+  }
   // ---- direct records: cE of the records whose columns had errors; did every prediction hold; is there anything to merge? ----------
   bool dir_pure = false;
   uint32_t dir_routed = 0;
@@ -4741,9 +4830,11 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
     DE.prefix = E.prefix; DE.prefix_len = E.prefix_len; DE.rg = E.rg; DE.rg_len = E.rg_len;
     DE.per_base_tags = P.per_base_tags; DE.cell0 = P.cell0; DE.cell1 = P.cell1;
     DE.n_slow = (uint32_t*)(misc + 44);
+    DE.meth_flag = P.meth_flag;
     DE_late = DE; late_emit = 1;
     do { last_launches++; hipLaunchKernelGGL(k_count_slow_duplex, dim3((n_slots + 255) / 256), dim3(256), 0, s, DE.ends, 0u, n_slots, DE.prefix_len, DE.rg_len, DE.n_slow); } while (0);
-    do { last_launches++; hipLaunchKernelGGL(k_emit_duplex_fast, dim3((n_slots + 3) / 4), dim3(256), 0, s, DE); } while (0);
+    if (meth_dup) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex_fast<1>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE); } while (0);
+    else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex_fast<0>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE); } while (0);
   } else if (direct) {
     if (!dir_pure) {
       // the merge: the families that left the split pipeline are written by k_emit from their descriptors, the directly written ones move
@@ -4761,6 +4852,10 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
     do { last_launches++; hipLaunchKernelGGL(k_meth_tail, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<MethSlot>(), d_offsets.as<uint64_t>(), out_ptr); } while (0);
     hip_check(hipGetLastError(), "k_meth_tail launch");
   }
+  if (meth_dup) {
+    do { last_launches++; hipLaunchKernelGGL(k_duplex_meth_tail, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<DuplexMethSlot>(), d_offsets.as<uint64_t>(), out_ptr); } while (0);
+    hip_check(hipGetLastError(), "k_duplex_meth_tail launch");
+  }
   hip_check(hipEventRecord(ev[3], s), "event");
   hip_check(hipEventRecord(c->ev1, s), "event");
   do { last_launches++; hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, s, d_statslots.as<unsigned long long>(), misc); } while (0);
@@ -4769,7 +4864,8 @@ int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, 
   FGX_SYNC(s);
   if (late_emit && (uint32_t)h_misc[44] != 0) {     // records the fast writer left: the per-field kernel, then the counters again (the CODEC writer counts bases)
     if (late_emit == 2) do { last_launches++; hipLaunchKernelGGL(k_emit_codec, dim3((n_slots + 3) / 4), dim3(256), 0, s, CE_late); } while (0);
-    else do { last_launches++; hipLaunchKernelGGL(k_emit_duplex, dim3((n_slots + 3) / 4), dim3(256), 0, s, DE_late); } while (0);
+    else if (meth_dup) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex<1>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE_late); } while (0);
+    else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex<0>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE_late); } while (0);
     hip_check(hipGetLastError(), "per-field record writer launch");
     do { last_launches++; hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, s, d_statslots.as<unsigned long long>(), misc); } while (0);
     hip_check(hipMemcpyAsync(h_misc, misc, sizeof(h_misc), hipMemcpyDeviceToHost, s), "D2H");

@@ -321,7 +321,8 @@ int fgx_run_bam_rejects(fgx_caller* c, const char* in_path, const char* out_path
         int prc = fgx_process_batch_device(c, base, batch_end, d_koff.p, d_klen.p, batch_rec, d_grp.p, batch_grp, &out, &n_def, &d_def);
         // --rejects: the device entry serves the callers through its side kernels (duplex / CODEC since round 6); what it refuses (a group outside their
         // scope: more than 128 records, malformed records; a duplex / CODEC batch with deferred molecules; FGX_REJECTS_DEVICE=0) goes through the host entry in one piece
-        // (and the methylation-aware mode, whose annotation runs on the general path: every batch of such a caller)
+        // (and the methylation-aware mode where the device entry refuses it — --trim, FGX_METH_DEVICE=0, no reference —, whose annotation then runs on the general
+        // path: every batch of such a caller; the simplex and duplex callers' mode otherwise stays on the device like any other batch)
         const bool host_whole = prc == 1 && (c->opt.track_rejects || c->opt.methylation_mode != FGX_METHYLATION_DISABLED);
         if (prc != 0 && !host_whole) throw std::runtime_error(c->err);
         const void* const rej_dev = host_whole ? nullptr : out.rejects;

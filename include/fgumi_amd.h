@@ -67,7 +67,10 @@ typedef struct fgx_options {
   uint8_t  overlapping_consensus;       /* 1: simplex/duplex default on */
   uint8_t  track_rejects;               /* 0 */
   uint8_t  methylation_mode;            /* FGX_METHYLATION_* (vanilla_caller.rs:323-326; --methylation-mode, simplex.rs:240-245); needs fgx_set_reference.
-                                           simplex and duplex only — CODEC has no methylation mode (codec_caller.rs:425) */
+                                           simplex and duplex only — CODEC has no methylation mode (codec_caller.rs:425).  Both callers' mode is decided by the
+                                           device-resident pipeline through every entry (no --trim, no --rejects; FGX_METH_DEVICE=0 opts out): what it defers —
+                                           simplex families outside the streaming kernels' shape, duplex molecules with a read of more than one CIGAR op — goes to
+                                           the general path, which knows the mode */
   uint8_t  _pad0[2];
   uint32_t min_reads;                   /* simplex --min-reads (required by the CLI) */
   int64_t  max_reads;                   /* -1 = None */
@@ -131,7 +134,8 @@ int fgx_libm_self_check(char* msg, uint64_t msg_cap);
  * the reference genome of the methylation-aware mode.  Contig i of the BAM header (= a record's ref_id) is seqs[i], lens[i] bases as the
  * FASTA holds them (any case).  seqs[i] == NULL stands for a contig the FASTA does not hold: an empty contig, every base unknown — the
  * caller-level `set_reference` accepts any provider; failing fast on missing contigs is the CLI loader's job (common.rs:131-141).  The sequences are copied into
- * HBM once (one byte per base; a human genome is 3.1 GB of the 288) and every batch's annotation kernel reads them there.  n_ref = 0
+ * HBM once (one byte per base; a human genome is 3.1 GB of the 288) and every batch's kernels read them there (the column kernels of the
+ * device-resident pipeline for both callers; the general path's annotation kernel for what they defer).  n_ref = 0
  * drops the reference.  With a methylation mode set and no reference, reads are called without annotation or tags, as the reference
  * does (annotate_and_normalize, vanilla_caller.rs:792-797).  Returns 0, or non-zero with fgx_last_error(c). */
 int fgx_set_reference(fgx_caller* c, uint32_t n_ref, const uint8_t* const* seqs, const uint64_t* lens);
@@ -406,7 +410,7 @@ typedef struct fgx_bam_run_stats {
   uint32_t boundary_repair_rounds, device_inflate;
   double seconds_device_deflate;                                                            /* inside the device stage (FGX_RUN_DEVICE_DEFLATE) */
   uint32_t device_deflate;
-  uint32_t host_entry_batches;                                                              /* batches that went through the host entry in one piece (deferred families without the subset way; --rejects / methylation the device entry refused) */
+  uint32_t host_entry_batches;                                                              /* batches that went through the host entry in one piece (deferred families without the subset way; --rejects, or the methylation-aware mode with --trim / FGX_METH_DEVICE=0, which the device entry refuses) */
 } fgx_bam_run_stats;
 #define FGX_RUN_HOST_INFLATE   1u   /* flags: inflate the BGZF blocks on the host cores (zlib) instead of on the device */
 #define FGX_RUN_DEVICE_DEFLATE 2u   /* flags: compress the consensus records on the device too (level 1 only; fgumi_amd/csrc/deflate_core.h, a lane
