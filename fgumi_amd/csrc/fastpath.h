@@ -232,7 +232,7 @@ struct FastPath {
   uint64_t last_packed_families = 0, last_classic_families = 0;   // families of the last batch finished by k_split_cols's packed build / by its classic builds (k_split_finish counts them)
   uint32_t last_split_build = 0;           // first-stage build of the last batch: 0 classic alone (or no split pipeline), 1 packed alone, 2 packed + partner launch
   uint32_t last_first_stage_retries = 0;   // families the first stage handed to the next launch
-  uint32_t last_launches = 0, last_host_syncs = 0;   // kernel launches (library scans not counted) / host synchronisations of the last run_once
+  uint32_t last_launches = 0, last_host_syncs = 0;   // kernel launches (library scans not counted) / host synchronisations of the last batch
   DevBuf d_dir_size, d_dir_off, d_dir_base, d_slot_desc, d_slot_err, d_out2, d_scan_tmp2;   // direct records (simplex_split.inc, fastpath.h)
   bool direct_off = false;                // a batch whose predicted record sizes did not hold: this caller stays on the scratch path (diagnostics: last_direct)
   uint64_t dir_cap_min = 0;               // output room a batch asked for beyond the first estimate
@@ -246,8 +246,6 @@ struct FastPath {
   uint32_t pool_slack = 256; bool pool_init = false;
   uint32_t pool_div = 8;                  // k_call_full's append lists hold 1 / pool_div of the column bound (halved when a batch exhausts them)
   static constexpr int RUN_AGAIN_LARGER_POOL = -77;   // (also: the batch again without / with more room for the direct records)
-  int run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, const uint64_t* d_rec_off, const uint32_t* d_rec_len, uint32_t n_rec,
-               const uint32_t* d_grp_first, uint32_t n_grp, FastResult* res);
   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: one flag per FastPath (= per caller = per device), not per process
   bool lds_attr_set = false, s2_attr_set = false, v2_attr_set = false;
   static constexpr int MAX_CHUNKS = 65;

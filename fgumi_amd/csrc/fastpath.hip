@@ -40,6 +40,8 @@
 #include "bamrec.h"
 #include "engine.h"
 #include <cstdlib>
+#include <memory>
+#include <string>
 #include <type_traits>
 #include "fastpath.h"
 #include "gate_core.h"
@@ -3991,8 +3993,12 @@ __global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, uns
 // -----------------------------------------------------------------------------------------------------
 // host driver
 // -----------------------------------------------------------------------------------------------------
-// diagnostics of a batch (fgx_debug_last_chain: bench.py's share_of_8 block): kernel launches and host synchronisations of FastPath::run_once
-#define FGX_SYNC(st) do { last_host_syncs++; hip_check(hipStreamSynchronize(st), "sync"); } while (0)
+// diagnostics of a batch (fgx_debug_last_chain: bench.py's share_of_8 block): kernel launches and host synchronisations of run_once
+#define FGX_SYNC(st) do { fp.last_host_syncs++; hip_check(hipStreamSynchronize(st), "sync"); } while (0)
+// every kernel launch of the driver: counted, and a refused launch is reported under its own kernel's name
+// (a macro around hipLaunchKernelGGL: tests/wavemu redefines that name to run the kernels on the CPU)
+#define FGX_LAUNCH(kernel, grid, block, lds, st, ...) do { fp.last_launches++; hipLaunchKernelGGL((kernel), grid, block, lds, st, __VA_ARGS__); hip_check(hipGetLastError(), #kernel " launch"); } while (0)
+
 void FastPath::release() {
   for (DevBuf* b : {&d_ends, &d_sizes, &d_offsets, &d_code, &d_qual, &d_depth, &d_err, &d_misc, &d_deferred, &d_out, &d_scan_tmp, &d_strings, &d_obs, &d_retry2,
                     &d_retry, &d_bound, &d_colbase, &d_statslots, &d_full_items, &d_full_count, &d_retry_old, &d_w2img, &d_famdesc, &d_fwimg,
@@ -4007,6 +4013,859 @@ void FastPath::release() {
   }
 }
 
+namespace {
+
+// ---- d_misc: the batch's counters, one 64-bit word each (a kernel gets the address of a word; u32 counters use its low half) ----------
+enum MiscWord : uint32_t {
+  MISC_STATS = 0,            // [0, FGX_STATS_LEN): the caller's counters, k_reduce_stats's sums over the slots; [1] = consensus reads written
+  MISC_COLS_USED = 28,
+  MISC_N_DEFERRED = 29,      // families on the deferred list
+  MISC_N_RETRY = 31,         // the retry list of the launch under way
+  MISC_N_RETRY_OLD = 32,     // k_simplex_wave2 → k_family_wave<0>
+  MISC_N_ROUTE = 33,         // k_split_cols → k_simplex_wave2
+  MISC_SMALL_RECS = 35,      // records in families of at most 64 records (k_col_bound)
+  MISC_DIR_FLAGS = 36,       // direct records: low half families whose records differ in size from the prediction, high half records past the room
+  MISC_N_BIG = 37,           // families of more than 64 records: k_family's list
+  MISC_N_DEEP = 38,          // families a pass of the streaming kernels hands on
+  MISC_BUILD_FAMILIES = 40,  // [40, 44): the slots' diagnostics (k_reduce_stats): families finished by k_split_cols's packed build, by its classic builds
+  MISC_N_SLOW = 44,          // duplex / CODEC: records the fast writer leaves to the per-field kernel
+  MISC_READ_BACK = 46,       // words the end of a batch copies to the host
+  MISC_WORDS = 48
+};
+constexpr uint32_t MISC_SPLIT_WINDOW = MISC_N_BIG - MISC_N_RETRY + 1;   // retry, route and big counts of a split stage come back as ONE copy
+static_assert(FGX_STATS_LEN <= MISC_COLS_USED && MISC_BUILD_FAMILIES == 40 && MISC_BUILD_FAMILIES + (32 - FGX_STATS_LEN) <= MISC_N_SLOW,
+              "k_reduce_stats writes words [0, FGX_STATS_LEN) and 40 .. of misc");
+static_assert(MISC_N_RETRY < MISC_N_ROUTE && MISC_N_ROUTE < MISC_N_BIG && MISC_SPLIT_WINDOW == 7 && MISC_N_SLOW < MISC_READ_BACK && MISC_READ_BACK <= MISC_WORDS, "misc layout");
+
+// ---- environment switches ---------------------------------------------------------------------------------------------------------------
+// fgx_knob: measurement knobs, a constant nullptr in the product library (engine.h); getenv: switches of the product
+inline bool env_not0(const char* e) { return !(e && e[0] == '0'); }
+inline bool env_is1(const char* e) { return e && e[0] == '1'; }
+inline int env_int(const char* e, int dflt) { return e ? atoi(e) : dflt; }
+inline uint32_t env_in(const char* e, int lo, int hi, uint32_t dflt) { const int v = e ? atoi(e) : 0; return v >= lo && v <= hi ? (uint32_t)v : dflt; }
+
+struct ProcessSwitches {   // read once per process, at the first batch
+  const bool v2 = env_not0(fgx_knob("FGX_V2")), seg = env_not0(fgx_knob("FGX_SEG"));
+  // (two families per wavefront measured slower than one at depth 8 — 14.9 vs 10.7 ms per 1 M families: the column phase costs
+  // the same per family and a CU holds 12 instead of 20 wavefronts; kept behind FGX_SEG2=1 for experiments)
+  const bool seg2 = env_is1(fgx_knob("FGX_SEG2"));
+  const bool early = env_not0(fgx_knob("FGX_S2_EARLY"));                 // 0: the first chunk's record kernel behind the column bound
+  const int chunks = env_int(getenv("FGX_SPLIT_CHUNKS"), 0);             // >= 1: chunks of the split pipeline
+  const int nosum = env_int(fgx_knob("FGX_S2_NOSUM"), 1);                // 0: every end through the f32 sums
+  const int packed = env_int(getenv("FGX_S2_PACKED"), 1);                // 0: the 64-column passes only
+  const int s2_debug = env_int(fgx_knob("FGX_S2_DEBUG"), 0);
+  const int pace = env_int(fgx_knob("FGX_S2_PACE"), 1);                  // 0: all record kernels up front
+  const uint32_t s2_bytes = env_in(fgx_knob("FGX_S2_BYTES"), 2048, 32768, 0) & ~15u, s2_wpb = env_in(fgx_knob("FGX_S2_WPB"), 1, 4, 0);
+  const int s2_partner = env_int(fgx_knob("FGX_S2_PARTNER"), -1);        // 1: always both first-stage kernels, 0: never
+  const int s2_fixed = env_int(fgx_knob("FGX_S2_FIXED"), -1);            // 0 / 1: the generic / the 160 + 80 build
+  const bool later_packed = env_not0(fgx_knob("FGX_S2_LATER_PACKED"));   // 0: the classic build in the later stages, as in round 5
+  const bool verbose = env_is1(fgx_knob("FGX_S2_VERBOSE"));
+  // wavefronts per workgroup of the first launch of k_simplex_seg / k_simplex_wave2 / k_family_wave.  k_simplex_wave2: the LDS of a workgroup
+  // is freed when its SLOWEST wavefront is done, so small workgroups keep more wavefronts running
+  const uint32_t seg_wpb = env_in(fgx_knob("FGX_SEG_WPB"), 1, WAVES_PER_BLOCK, WAVES_PER_BLOCK), w2_wpb = env_in(fgx_knob("FGX_W2_WPB"), 1, WAVES_PER_BLOCK, FGX_W2_WPB_DEFAULT),
+                 fw_wpb = env_in(fgx_knob("FGX_FW_WPB"), 1, WAVES_PER_BLOCK, WAVES_PER_BLOCK);
+};
+struct BatchSwitches {     // read at the start of every batch: tests and tools switch these inside one process
+  const char* const split_env = getenv("FGX_SPLIT");
+  const bool split = env_not0(split_env);                                // FGX_SPLIT=0 / 2: never / always the split pipeline
+  const int split_mode = env_int(split_env, 1);
+  const bool direct = env_is1(getenv("FGX_DIRECT"));                     // (tools/direct_check.py switches it between two runs of one process)
+  const bool deep = env_not0(getenv("FGX_DEEP"));
+  const uint32_t seg_bytes = env_in(fgx_knob("FGX_SEG_BYTES"), 4096, 32768, 11776) & ~63u;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
+  const uint32_t wave_bytes = env_in(fgx_knob("FGX_WAVE_BYTES"), 1024, 22016, 0) & ~15u;     // tuning knobs (0: the FastPath's own value)
+  const uint32_t lds_tile_large = env_in(fgx_knob("FGX_LDS_TILE_LARGE"), 16384, 163840, 0) & ~15u;
+  const uint32_t split_fpw = env_in(fgx_knob("FGX_SPLIT_FPW"), 1, 32, 0);
+};
+
+#define FGX_LDS_ATTR(bytes, ...) lds_attr((const void*)__VA_ARGS__, bytes, #__VA_ARGS__)
+void lds_attr(const void* kernel, int bytes, const char* name) {
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) hip_check(e, (std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) for ") + name + ": the device refused the dynamic LDS size").c_str());
+}
+
+struct Slice { uint32_t bytes, wpb; int build; };   // one launch of a chain: LDS slice of a wavefront, wavefronts per workgroup, which build of the kernel
+
+// ---- k_split_cols: which builds, over which slices -------------------------------------------------------------------------------------
+struct SplitBuild { bool packed, partner; std::vector<Slice> stages; };   // (Slice.build: 1 = rows of 160 + 80 bytes as immediates)
+// From the tile strides of a sample of families (64 spread evenly over the first chunk: the head of a coordinate-sorted file need not look
+// like the rest) and the caller's options.  `packed_ok`: the options allow the packed pass at all.
+SplitBuild choose_split_build(const SplitFam* sample, uint32_t n_sample, double mean_recs, bool packed_ok, uint32_t nsafe, const ProcessSwitches& ps) {
+  SplitBuild B;
+  // which of the two first-stage kernels the batch needs (a family of the other kind still finds its way: the packed kernel without a
+  // partner hands it to the next launch, the partner kernel alone IS the classic kernel)
+  uint32_t n_pk = 0, n160 = 0;
+  for (uint32_t i = 0; i < n_sample; i++) {
+    const SplitFam& F = sample[i];
+    auto ok = [&](uint32_t m) { return m < 2u || (m >= nsafe && m <= S2_PACKED_MAX_ROWS); };
+    n_pk += (packed_ok && ok(F.m_a) && ok(F.m_b) && ((F.len_a + 7u) >> 3) + ((F.len_b + 7u) >> 3) <= 64u) ? 1u : 0u;
+    n160 += (F.qs == 160 && F.ss == 80) ? 1u : 0u;
+  }
+  B.packed = packed_ok && !(n_sample && 100ull * n_pk < (unsigned long long)n_sample);   // under 1 % of its shape: the classic kernel alone
+  B.partner = B.packed && (ps.s2_partner >= 0 ? ps.s2_partner != 0 : 100ull * n_pk < 99ull * n_sample);
+  // LDS slice of the first launch: the MEAN family's tile (rows of 160 + 80 bytes) + room for its k_call_full items, at least the
+  // 4352 bytes of a 16-record family — a deeper library starts at the slice its families need instead of failing the first launch
+  // as a whole (depth 12: every family took two launches, 32 ms per 1 M families).
+  // (round 5: the packed pass sends every column it does not answer itself to k_call_full — also the one-base columns of too few
+  // observations, which run_cols's gates answer — and keeps an 8-byte descriptor per such column at the top of the slice: 56 bytes per
+  // column, ~14 columns per depth-8 family of `simulate` data; 5632 bytes x 4 wavefronts still leave a CU six workgroups)
+  uint32_t bytes0 = B.packed ? 5632 : 4352;
+  const uint32_t mean_need = (uint32_t)(mean_recs + 0.999) * 240u + 16u + (B.packed ? 1680u : 400u);
+  if (mean_need > bytes0) bytes0 = std::min<uint32_t>((mean_need + 15u) & ~15u, 17408u);
+  if (ps.s2_bytes) bytes0 = ps.s2_bytes;
+  const uint32_t wpb0 = ps.s2_wpb ? ps.s2_wpb : (bytes0 <= 6528u ? 4u : bytes0 <= 13056u ? 2u : 1u);
+  // rows of 160 + 80 bytes (reads up to 160 bases) have their own build: member rows at immediate offsets in the column loop.  Every slice
+  // size in that build, then ONE launch of the generic build for the families with other strides (round 3 ran the generic build from the
+  // second slice on — a long-tail batch spends most of its column time there)
+  const int fixed = (ps.s2_fixed >= 0 ? ps.s2_fixed != 0 : 2 * n160 > n_sample) ? 1 : 0;
+  const Slice all[5] = {{bytes0, wpb0, fixed}, {std::max(2 * bytes0, 8704u), 2u, fixed}, {17408u, 1u, fixed}, {34816u, 1u, fixed}, {34816u, 1u, 0}};
+  for (int i = 0; i < (fixed ? 5 : 4); i++)   // (a slice no larger than the one before it, in the same build, has nothing to add)
+    if (i == 0 || all[i - 1].build != all[i].build || all[i].bytes > all[i - 1].bytes) B.stages.push_back(all[i]);
+  return B;
+}
+
+// ---- one batch ---------------------------------------------------------------------------------------------------------------------------
+// What the stages of a batch share: the caller and its input, both streams, the route the batch takes, the kernels' base parameters, and
+// the family list that one stage hands to the next.  A stage enqueues on `s` (the split pipeline also on the second stream `fp.s2`).
+struct Batch {
+  // (an aggregate: run_once gives the first line, the rest follows from it)
+  FastPath& fp; fgx_caller* const c; const uint8_t* const d_blob; const uint64_t blob_len; const uint64_t* const d_rec_off; const uint32_t* const d_rec_len; const uint32_t n_rec;
+  const uint32_t* const d_grp_first; const uint32_t n_grp; FastResult* const res; const ProcessSwitches& ps;
+  const BatchSwitches sw{};
+  const fgx_options& o = c->opt;
+  const hipStream_t s = c->stream;
+  // ---- the route ----
+  const bool duplex = o.caller_kind == FGX_CALLER_DUPLEX, codec = o.caller_kind == FGX_CALLER_CODEC;
+  const bool meth_on = !o.trim && o.methylation_mode != FGX_METHYLATION_DISABLED && c->genome != nullptr;
+  // Methylation-aware mode (simplex, a reference set, no --trim): the streaming kernels of simplex_deep.inc are the whole pipeline — every
+  // family on their list, the reference lookup / counts / normalisation in k_deep_cols<1>, MM / ML / cu / ct behind the standard record
+  // (k_meth_sizes, k_meth_tail); a family outside their shape is deferred to the general path, which knows the mode.
+  const bool meth_dev = !duplex && !codec && meth_on;
+  // The duplex caller in the mode: the wavefront kernel's <1, 1> build annotates and normalises the four read sets of a molecule in its column
+  // loops, the record writers' <1> builds apply the conversion-artifact rule, am/au/at, bm/bu/bt, MM/ML/cu/ct follow RX (duplex_meth.inc).
+  const bool meth_dup = duplex && meth_on;
+  // Simplex without --trim: which head of the launch chain?  Shallow families (the mean family fits a quarter of a wave's LDS
+  // slice) start at k_simplex_seg<4>; everything else at the split pipeline (k_split_parse + k_split_cols, simplex_split.inc),
+  // whose record kernel also leaves what k_col_bound would (column bound, byte-span descriptor).
+  const bool simplex_v2 = !duplex && !codec && !o.trim && ps.v2 && !meth_dev;
+  const double mean_span = (double)blob_len / (double)n_grp + 48.0;   // mean bytes of a family + alignment / read-ahead slack
+  const double mean_recs = (double)n_rec / (double)n_grp;
+  const bool seg4 = simplex_v2 && ps.seg && mean_span + (16 * 8 + 64) <= sw.seg_bytes / 4;
+  bool use_split = false, direct = false;   // (known after the column bound's synchronisation)
+  // ---- sizes, buffers ----
+  const uint32_t n_slots = 3 * n_grp;       // simplex: Fragment, R1, R2 of each family; duplex: slot 0 unused, R1, R2
+  uint64_t col_cap = 0, dir_cap = 0; uint32_t full_cap = 0;
+  unsigned long long* misc = nullptr;
+  uint32_t* cnt(MiscWord w) const { return (uint32_t*)(misc + w); }
+  FastParams P;                             // the kernels' parameters; a launch works on a copy with its list and slice
+  // the split pipeline: families per wavefront of the record kernel, chunks, families per chunk; the record kernel's parameters
+  uint32_t fpw = 0, n_chunks = 0, chunk_fam_raw = 0, chunk_fam = 0;
+  FastParams PK;
+  bool early_parse = false;
+  bool s2_busy = false, s2_joining = false;   // work enqueued on the second stream / `s` waits for the last of it, the host has not yet waited for `s`
+  // ---- what a stage hands to the next ----
+  // the list of families the next stage takes (nullptr: all, in file order), and the two retry lists the stages fill in turn
+  uint32_t* lists[2] = {nullptr, nullptr};
+  const uint32_t* cur_list = nullptr; uint32_t n_cur = 0; int out_list = 0;
+  uint32_t h_route_seen = 0, h_big_seen = 0; bool split_counts_seen = false;   // what the split stages' last synchronisation read
+  uint32_t n_big = 0; const uint32_t* big_list = nullptr;                      // families of more than 64 records
+  uint64_t n_full = 0;
+  bool dir_pure = false; uint32_t dir_routed = 0; uint64_t dir_total = 0;      // direct records
+  uint64_t out_len = 0; uint8_t* out_ptr = nullptr;
+
+  // A stage that throws (a refused allocation, a failed call) unwinds while the second stream may still read the caller's records and
+  // write the split descriptors: wait for it.  Nothing to do on the regular ways out: they lie behind a synchronisation of `s` that
+  // followed the join.
+  ~Batch() { if (s2_busy) (void)hipStreamSynchronize(fp.s2); }
+
+  void sync() { FGX_SYNC(s); if (s2_joining) { s2_busy = false; s2_joining = false; } }
+  void join_s2(hipEvent_t ev) { hip_check(hipStreamWaitEvent(s, ev, 0), "wait"); s2_joining = true; }
+  void scan_u64(uint64_t* in, uint64_t* out, uint32_t n, const char* what) {
+    size_t tb = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, s);
+    fp.d_scan_tmp.reserve(tb);
+    hip_check(hipcub::DeviceScan::ExclusiveSum(fp.d_scan_tmp.p, tb, in, out, (int)n, s), what);
+  }
+  // The tables of a caller never change: one image of a kernel's LDS tables per FastPath, built on the host by the first batch that needs it
+  template <class Image> const void* table_image(DevBuf& d, void (*build)(Image&, const ConsensusTables&), const char* what) {
+    if (!d.p) {
+      const auto img = std::make_unique<Image>();
+      build(*img, c->h_tables.t);
+      d.reserve(sizeof(Image));
+      hip_check(hipMemcpyAsync(d.p, img.get(), sizeof(Image), hipMemcpyHostToDevice, s), what);
+      sync();   // (the host copy ends with this scope)
+    }
+    return d.p;
+  }
+  // a launch over the current list with an LDS slice of `bytes` per wavefront (`retry`: what does not fit goes on the other list; else it is deferred)
+  FastParams stage_params(uint32_t bytes, bool retry) {
+    hip_check(hipMemsetAsync(cnt(MISC_N_RETRY), 0, 4, s), "memset");
+    FastParams PS = P;
+    PS.group_list = cur_list; PS.lds_wave_bytes = bytes;
+    PS.retry = retry ? lists[out_list] : nullptr; PS.n_retry = cnt(MISC_N_RETRY);
+    return PS;
+  }
+  void next_list(uint32_t n) { cur_list = lists[out_list]; n_cur = n; out_list ^= 1; }
+
+  // ---- buffers, counters, events ----
+  void set_up() {
+    fp.last_meth_device = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
+    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
+    fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
+    fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
+    fp.d_offsets.reserve(((size_t)n_slots + 1) * 8);
+    fp.d_deferred.reserve((size_t)n_grp * 4);
+    fp.d_misc.reserve(MISC_WORDS * 8);
+    hip_check(hipMemsetAsync(fp.d_misc.p, 0, MISC_WORDS * 8, s), "memset");
+    misc = fp.d_misc.as<unsigned long long>();
+    const std::string strs = c->prefix + c->rg;   // strings: prefix | rg
+    fp.d_strings.reserve(strs.size() + 16);
+    if (!strs.empty()) hip_check(hipMemcpyAsync(fp.d_strings.p, strs.data(), strs.size(), hipMemcpyHostToDevice, s), "H2D strings");
+    for (int i = 0; i < 4; i++) if (!fp.ev[i]) hip_check(hipEventCreate(&fp.ev[i]), "hipEventCreate");
+    // column scratch: deterministic per-family slots from an exclusive scan of the column bound
+    fp.d_bound.reserve(((size_t)n_grp + 1) * 8); fp.d_colbase.reserve(((size_t)n_grp + 1) * 8);
+    fp.d_statslots.reserve((size_t)STAT_SLOTS * 32 * 8);
+    hip_check(hipMemsetAsync(fp.d_statslots.p, 0, (size_t)STAT_SLOTS * 32 * 8, s), "memset");
+    fp.d_famdesc.reserve((size_t)n_grp * 16);
+    hip_check(hipEventRecord(c->ev0, s), "event");
+    hip_check(hipEventRecord(fp.ev[0], s), "event");   // the family stage: record kernel / column bound, scan, family kernels, k_call_full
+    // split pipeline: as many families per wavefront of the record kernel as fill its 64 lanes on average;
+    // chunks of at least ~150 000 families (a column kernel of 37 500 workgroups: 20 rounds of the chip's resident workgroups, so that its tail — the
+    // last round runs with a part of the chip — stays a few per cent), eight at most: one rank's share of an 8-way strong-scaling run (625 000
+    // families) took 8 chunks of 78 000 until round 6 and spent a third of its step in launch gaps and kernel tails (bench.py share_of_8)
+    fpw = mean_recs >= 1.0 ? (uint32_t)(64.0 / mean_recs) : 16u;
+    fpw = fpw < 1u ? 1u : fpw > 16u ? 16u : fpw;
+    if (sw.split_fpw) fpw = sw.split_fpw;
+    n_chunks = ps.chunks >= 1 ? (uint32_t)ps.chunks : std::min<uint32_t>(8u, std::max<uint32_t>(1u, n_grp / 150000u));
+    if (n_chunks > (uint32_t)FastPath::MAX_CHUNKS - 1) n_chunks = FastPath::MAX_CHUNKS - 1;   // (the last event marks where the second stream starts)
+    chunk_fam_raw = (n_grp + n_chunks - 1) / n_chunks;
+    chunk_fam = ((chunk_fam_raw + 4 * fpw - 1) / (4 * fpw)) * (4 * fpw);      // whole workgroups of both kernels per chunk
+  }
+
+  // ---- column bound, its scan, and the one synchronisation every batch has: which route, how much room ----
+  void bound_columns() {
+    FGX_LAUNCH(k_col_bound, dim3((n_grp + 1023) / 1024), dim3(1024), 0, s, d_grp_first, d_rec_len, d_rec_off, n_grp, fp.d_bound.as<uint64_t>(), duplex ? 4u : codec ? 2u : 3u,
+               fp.d_famdesc.as<uint4>(), misc + MISC_SMALL_RECS, fp.d_sizes.as<uint64_t>() + n_slots);
+    scan_u64(fp.d_bound.as<uint64_t>(), fp.d_colbase.as<uint64_t>(), n_grp + 1, "scan bound");
+    // (round 6: every small device-to-host copy costs the stream ~25 us, timeline of the 625 000-family step — so the total is the scan's own last element)
+    uint64_t col_total = 0;
+    hip_check(hipMemcpyAsync(&col_total, fp.d_colbase.as<uint64_t>() + n_grp, 8, hipMemcpyDeviceToHost, s), "D2H");
+    unsigned long long small_recs = 0;
+    hip_check(hipMemcpyAsync(&small_recs, misc + MISC_SMALL_RECS, 8, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    // The split pipeline is the faster head for every family it keeps (depth 8: 25.7 against 37 ms per 5 M families) — since round 4 that is
+    // every family of up to 64 records in the common shape (an end of more than 16 reads sends its disagreeing columns to k_call_full as
+    // several items); larger families it only measures and hands to k_family.  Split when at least half of the reads sit in families of
+    // at most 64 records (FGX_SPLIT=0 / 2: never / always).
+    use_split = simplex_v2 && sw.split && !seg4 && (sw.split_mode == 2 || (double)small_recs >= 0.5 * (double)n_rec);
+    // Direct records (fastpath.h): the split pipeline's column kernel writes the consensus records itself (FGX_DIRECT=1).  Byte-identical on
+    // the GPU (tools/direct_check.py, tests/test_gpu_direct_records.py), but NOT the default: measured on 5 M depth-8 families the column kernel
+    // pays for the emission what k_emit cost as a kernel of its own (k_split_cols 2.82 -> 3.82 ms per chunk, k_split_parse 0.94 -> 1.41 ms with the
+    // size prediction; step 33.7 -> 40.2 ms with the merge, ~34 ms without: profiles/r04_experiments.md) — vector-instruction issue is what the
+    // stage is short of, and the record's constant bytes cost as many instructions written from here as from there.
+    direct = use_split && sw.direct && !fp.direct_off && !meth_dev;
+    if (early_parse && !use_split) join_s2(fp.ev_chunk[0]);   // (its descriptors are not used; nothing of this batch may still run when the call returns)
+    col_cap = col_total + 64;
+    if (direct) {
+      // room for the records: 6 bytes per column of the (generous) column bound covers sequence + qualities + cd + ce twice over for
+      // simulate-shaped reads; names and tags come on top.  A batch that needs more says so (dir_flags[1]) and runs again with what it asked for.
+      dir_cap = std::max<uint64_t>(col_cap * 6 + (uint64_t)n_slots * 64 + 4096, fp.dir_cap_min);
+      fp.d_out.reserve(dir_cap + 64);
+      fp.d_dir_size.reserve((size_t)n_grp * 4 + 64); fp.d_dir_off.reserve((size_t)n_grp * 8 + 64); fp.d_dir_base.reserve((FastPath::MAX_CHUNKS + 2) * 8);
+      fp.d_slot_desc.reserve((size_t)n_slots * sizeof(SlotDesc)); fp.d_slot_err.reserve((size_t)n_slots * 4);
+      hip_check(hipMemsetAsync(fp.d_dir_size.p, 0, (size_t)n_grp * 4, s), "memset");
+      hip_check(hipMemsetAsync(fp.d_dir_base.p, 0, (FastPath::MAX_CHUNKS + 2) * 8, s), "memset");
+      hip_check(hipMemsetAsync(fp.d_slot_err.p, 0, (size_t)n_slots * 4, s), "memset");
+      hip_check(hipMemsetAsync(fp.d_sizes.p, 0, ((size_t)n_slots + 1) * 8, s), "memset");
+    }
+    fp.d_code.reserve(col_cap + 64); fp.d_qual.reserve(col_cap + 64); fp.d_err.reserve(col_cap * 2 + 64);   // (+ slack: k_emit reads whole dwords)
+    if (meth_dev || meth_dup) {
+      fp.d_mflag.reserve(col_cap + 64); fp.d_mu.reserve(col_cap * 2 + 64); fp.d_mt.reserve(col_cap * 2 + 64);
+      fp.d_mslot.reserve((size_t)n_slots * (meth_dup ? sizeof(DuplexMethSlot) : sizeof(MethSlot)) + 64);
+    }
+    if (duplex) fp.d_obs.reserve(col_cap * 4); else fp.d_depth.reserve(col_cap * 2 + 64);
+  }
+
+  // ---- the kernels' base parameters, the call_full pool, the retry lists ----
+  void fill_params() {
+    memset(&P, 0, sizeof(P));
+    P.blob = d_blob; P.rec_off = d_rec_off; P.rec_len = d_rec_len; P.grp_first = d_grp_first;
+    P.blob_len = blob_len;
+    P.T = c->d_tables.as<DeviceTables>(); P.TU = c->d_umi_tables.as<DeviceTables>();
+    P.fw_image = table_image<FwLds>(fp.d_fwimg, build_fw_image, "H2D fw image");   // k_family_wave's LDS block
+    P.min_reads = o.min_reads; P.max_reads = o.max_reads;
+    P.min_input_bq = o.min_input_base_quality; P.min_cons_bq = o.min_consensus_base_quality;
+    // k_split_cols's sum-free observation step: from how many agreeing observations a column is the cap whatever their qualities (gate_core.h)
+    P.s2_packed = (ps.packed ? 1u : 0u) | ((ps.packed && ps.s2_debug) ? 2u : 0u);
+    P.s2_nsafe = ps.nosum ? unanimous_cap_depth(c->h_tables.t, (uint32_t)o.min_input_base_quality & 0xFFu, 64u) : FGX_NEVER_CAP;
+    P.trim = o.trim; P.overlap = o.overlapping_consensus;
+    if (duplex) {   // single-strand caller of the duplex caller (duplex_caller.rs:474-489): min_reads 1, min consensus base quality 2
+      P.min_reads = 1; P.max_reads = -1; P.min_cons_bq = FGX_MIN_PHRED;
+      P.dmin_total = o.duplex_min_reads[0]; P.dmin_xy = o.duplex_min_reads[1]; P.dmin_yx = o.duplex_min_reads[2];
+      P.dmax_reads = o.duplex_max_reads_per_strand;
+      P.col_obs = fp.d_obs.as<uint32_t>(); P.dends = fp.d_ends.as<DuplexDesc>();
+    }
+    if (codec) {    // single-strand caller of the CODEC caller (codec_caller.rs:374-397): min_reads 1, no cap, min consensus base quality 0
+      P.min_reads = 1; P.max_reads = -1; P.min_cons_bq = 0; P.trim = 0; P.overlap = 0;
+      P.cends = fp.d_ends.as<CodecDesc>(); P.cmin_reads = o.codec_min_reads_per_strand; P.cmax_reads = o.codec_max_reads_per_strand;
+      P.cmin_duplex_len = o.codec_min_duplex_length;
+    }
+    P.per_base_tags = o.produce_per_base_tags; P.track_rejects = o.track_rejects;
+    P.tag0 = (duplex || codec) ? 'M' : o.tag[0]; P.tag1 = (duplex || codec) ? 'I' : o.tag[1]; P.cell0 = o.cell_tag[0]; P.cell1 = o.cell_tag[1];
+    P.prefix_len = (uint32_t)c->prefix.size(); P.rg_len = (uint32_t)c->rg.size();
+    P.ends = fp.d_ends.as<EndDesc>(); P.rec_sizes = fp.d_sizes.as<uint64_t>();
+    P.col_code = fp.d_code.as<uint8_t>(); P.col_qual = fp.d_qual.as<uint8_t>(); P.col_depth = fp.d_depth.as<uint16_t>(); P.col_err = fp.d_err.as<uint16_t>();
+    if (meth_dev || meth_dup) {
+      const GenomeRef* gr = c->genome.get();
+      const uint32_t n_ref = (uint32_t)gr->off.size();
+      fp.d_mcontigs.reserve((size_t)(n_ref + 1) * 16 + 64);
+      if (n_ref) {
+        hip_check(hipMemcpyAsync(fp.d_mcontigs.p, gr->off.data(), (size_t)n_ref * 8, hipMemcpyHostToDevice, s), "H2D contig offsets");
+        hip_check(hipMemcpyAsync(fp.d_mcontigs.as<uint64_t>() + n_ref, gr->len.data(), (size_t)n_ref * 8, hipMemcpyHostToDevice, s), "H2D contig lengths");
+      }
+      P.meth_mode = o.methylation_mode; P.n_ref = n_ref; P.genome = (const uint8_t*)gr->d_genome.p;
+      P.contig_off = fp.d_mcontigs.as<uint64_t>(); P.contig_len = fp.d_mcontigs.as<uint64_t>() + n_ref;
+      P.meth_flag = fp.d_mflag.as<uint8_t>(); P.meth_u = fp.d_mu.as<uint16_t>(); P.meth_t = fp.d_mt.as<uint16_t>();
+    }
+    P.col_base = fp.d_colbase.as<uint64_t>();
+    if (direct) {
+      P.dir_size = fp.d_dir_size.as<uint32_t>(); P.dir_off = fp.d_dir_off.as<uint64_t>(); P.out = fp.d_out.as<uint8_t>(); P.out_cap = dir_cap;
+      P.out_off = fp.d_offsets.as<uint64_t>(); P.slot_desc = fp.d_slot_desc.as<SlotDesc>(); P.slot_err = fp.d_slot_err.as<uint32_t>();
+      P.strings = fp.d_strings.as<char>(); P.dir_flags = cnt(MISC_DIR_FLAGS);
+    }
+    P.stats = fp.d_statslots.as<unsigned long long>(); P.n_deferred = cnt(MISC_N_DEFERRED);
+    P.deferred = fp.d_deferred.as<uint32_t>();
+    fp.d_retry.reserve((size_t)n_grp * 4);
+    P.retry = fp.d_retry.as<uint32_t>(); P.n_retry = cnt(MISC_N_RETRY);
+    // append lists for the columns that need call_full: room for 1 / pool_div of the column bound (overflow → general path)
+    const uint64_t full_total = col_cap / fp.pool_div + (uint64_t)N_LISTS * fp.pool_slack;
+    full_cap = (uint32_t)std::min<uint64_t>(full_total / N_LISTS, 0x7FFFFFFFull);
+    fp.d_full_items.reserve((size_t)full_cap * N_LISTS * sizeof(FullItem));
+    fp.d_full_count.reserve((size_t)N_LISTS * 4);
+    hip_check(hipMemsetAsync(fp.d_full_count.p, 0, (size_t)N_LISTS * 4, s), "memset");
+    P.full_items = fp.d_full_items.as<FullItem>(); P.full_count = fp.d_full_count.as<uint32_t>(); P.full_cap = full_cap;
+    P.lds_wave_bytes = sw.wave_bytes ? sw.wave_bytes : duplex ? fp.lds_wave_bytes_duplex : codec ? fp.lds_wave_bytes_codec : fp.lds_wave_bytes;
+    P.lds_tile_bytes = fp.lds_tile_bytes_large;
+    if (!fp.lds_attr_set) {
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<0>);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1>);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<2>);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1, 1>);
+      fp.lds_attr_set = true;
+    }
+    fp.d_retry2.reserve((size_t)n_grp * 4);
+    lists[0] = fp.d_retry.as<uint32_t>(); lists[1] = fp.d_retry2.as<uint32_t>();
+    // simplex families of more than 64 records: no wavefront-per-family kernel takes them — the first kernel that sees one puts it on
+    // k_family's list (round 3 walked them through k_simplex_wave2 and three k_family_wave<0> launches first: 2 ms per 1 M long-tail families)
+    // (not with direct records: their merge pass walks ONE list of the families that left the split pipeline — the route list)
+    if (!duplex && !codec && !direct) { fp.d_big.reserve((size_t)n_grp * 4); P.big = fp.d_big.as<uint32_t>(); P.n_big = cnt(MISC_N_BIG); }
+    n_cur = meth_dev ? 0u : n_grp;       // (methylation-aware mode: no wavefront-per-family kernel runs)
+  }
+
+  // Wave-per-family launches over growing LDS slices: everything first, then only the groups whose records did not fit
+  // (long-tail families: 6 KB holds ~18 records of 150 bp, 12 KB ~36, 22 KB all 64 a wavefront can take).
+  // Fewer wavefronts per workgroup as the slices grow: the LDS a workgroup asks for is what limits the wavefronts a CU holds
+  // (4 x 22 KB = one workgroup = 4 waves per CU; 1 x 22 KB = six workgroups = 6 waves)
+  void wave_slices(std::vector<Slice>& st, uint32_t first_wpb) const {
+    const uint32_t bytes[3] = {P.lds_wave_bytes, 12288u, 22016u};
+    for (int i = 0; i < 3; i++) if (i == 0 || bytes[i] > bytes[i - 1]) st.push_back({bytes[i], i == 0 ? first_wpb : i == 1 ? 2u : 1u, 1});
+  }
+  // One launch per slice over the current list: a family that does not fit the slice goes on the launch's retry list, which the next launch
+  // takes (`keep_last`: the last one leaves such a list too, for the stage behind the chain; else its families are deferred).  The host
+  // learns the length of the next list from a 4-byte copy behind each launch.
+  template <class Launch> void run_slices(const std::vector<Slice>& st, bool keep_last, Launch launch) {
+    for (size_t i = 0; i < st.size() && n_cur; i++) {
+      FastParams PS = stage_params(st[i].bytes, i + 1 < st.size() || keep_last);
+      launch(st[i], PS);
+      uint32_t n_next = 0;
+      hip_check(hipMemcpyAsync(&n_next, cnt(MISC_N_RETRY), 4, hipMemcpyDeviceToHost, s), "D2H");
+      sync();
+      next_list(PS.retry ? n_next : 0);
+    }
+  }
+
+  // ---- split pipeline: k_split_parse, chunk by chunk on the second stream, under k_split_cols of the chunk before; k_split_finish ----
+  void split_pipeline() {
+    // k_split_cols over growing LDS slices (4 / 2 / 1 / 1 wavefronts per workgroup); what it does not take is collected in
+    // `route` and starts the k_simplex_wave2 chain
+    if (!fp.s2_attr_set) {
+      FGX_LDS_ATTR(65536, k_split_cols<0, 0, 0, 0>);
+      FGX_LDS_ATTR(65536, k_split_cols<160, 80, 0, 0>);
+      FGX_LDS_ATTR(65536, k_split_cols<0, 0, 0, 1>);
+      FGX_LDS_ATTR(65536, k_split_cols<160, 80, 0, 1>);
+      FGX_LDS_ATTR(65536, k_split_cols<0, 0, 0, 2>);
+      FGX_LDS_ATTR(65536, k_split_cols<160, 80, 0, 2>);
+      FGX_LDS_ATTR(65536, k_split_cols<0, 0, 1, 0>);
+      FGX_LDS_ATTR(65536, k_split_cols<160, 80, 1, 0>);
+      fp.s2_attr_set = true;
+    }
+    P.s2_image = table_image<S2Image>(fp.d_s2img, build_s2_image, "H2D s2 image");
+    fp.d_route.reserve((size_t)n_grp * 4);
+    fp.d_split_out.reserve((size_t)n_grp * sizeof(SplitOut));
+    if (!early_parse) prepare_parse();
+    P.fam_desc = fp.d_famdesc.as<uint4>();
+    P.split_rec = fp.d_split_rec.as<SplitRec>(); P.split_fam = fp.d_split_fam.as<SplitFam>(); P.split_out = fp.d_split_out.as<SplitOut>();
+    P.route = fp.d_route.as<uint32_t>(); P.n_route = cnt(MISC_N_ROUTE);
+    if (direct) { PK.dir_size = P.dir_size; PK.min_input_bq = o.min_input_base_quality; PK.per_base_tags = o.produce_per_base_tags; PK.rg_len = (uint32_t)c->rg.size(); }
+    fp.last_split_chunks = n_chunks;
+    fp.dir_chunks_run = (n_grp + chunk_fam_raw - 1) / chunk_fam_raw;     // chunks that hold families (the rounding of chunk_fam can leave the last ones empty)
+    fork_s2();
+    size_t dir_scan_bytes = 0;
+    if (direct) {
+      const DirSizeIn in(fp.d_dir_size.as<uint32_t>(), DirCast());
+      (void)hipcub::DeviceScan::ExclusiveSum(nullptr, dir_scan_bytes, in, fp.d_dir_off.as<uint64_t>(), (int)std::min<uint64_t>(chunk_fam, n_grp), fp.s2);
+      fp.d_scan_tmp2.reserve(dir_scan_bytes + 64);
+    }
+    if (!early_parse) launch_parse(0, dir_scan_bytes);
+    // the sample that picks the builds: one strided copy of at most one row per family of the first chunk (the rows past it are not
+    // parsed yet and hold what the previous batch left)
+    SplitFam fam_sample[64];
+    const uint32_t sample_span = (uint32_t)std::min<uint64_t>(chunk_fam, n_grp), sample_stride = std::max<uint32_t>(1u, sample_span / 64u);
+    const uint32_t n_sample = sample_span < 64u ? sample_span : 64u;
+    hip_check(hipMemcpy2DAsync(fam_sample, sizeof(SplitFam), fp.d_split_fam.p, (size_t)sample_stride * sizeof(SplitFam), sizeof(SplitFam), n_sample, hipMemcpyDeviceToHost, fp.s2), "D2H sample");
+    hip_check(hipEventRecord(fp.ev_sample, fp.s2), "event");
+    // (round 5) the record kernel is bound by HBM bandwidth (it reads the whole blob: 4.2 TB/s alone on the chip), and a column kernel
+    // beside it gets what is left — with every chunk's record kernel queued up front, the first column kernel took 6.9 ms instead of
+    // 1.7 and the two streams added up like one (profiles/r05_timeline_*.txt).  Paced: chunk k + 2 is parsed
+    // when the column kernel of chunk k has finished, i.e. under the column kernel of chunk k + 1.
+    const bool paced = ps.pace != 0 && n_chunks > 2;
+    for (uint32_t ci = 1; ci < (paced ? 2u : n_chunks); ci++) launch_parse(ci, dir_scan_bytes);
+    fp.last_host_syncs++;
+    hip_check(hipEventSynchronize(fp.ev_sample), "sync");
+    const bool packed_ok = !direct && P.s2_packed != 0 && P.s2_nsafe != FGX_NEVER_CAP && P.min_reads <= P.s2_nsafe && ((uint32_t)P.min_input_bq & 0xFFu) <= 128u;   // (what run_cols_packed asks of the caller's options)
+    const SplitBuild B = choose_split_build(fam_sample, n_sample, mean_recs, packed_ok, P.s2_nsafe, ps);
+    fp.last_split_build = B.packed ? (B.partner ? 2u : 1u) : 0u;
+    cur_list = nullptr; n_cur = n_grp; out_list = 0;
+    for (size_t ci = 0; ci < B.stages.size() && n_cur; ci++) {
+      const Slice& S = B.stages[ci];
+      FastParams PS = stage_params(S.bytes, ci + 1 < B.stages.size());
+      PS.s2_partner = (B.partner || (ci > 0 && ps.later_packed && B.packed)) ? 1u : 0u;
+      const bool pair_build = B.packed && (ci == 0 || ps.later_packed);
+      if (ci == 0) {   // the first stage takes the families in file order, chunk by chunk behind the record kernel
+        for (uint32_t k = 0; k < n_chunks; k++) {
+          const uint32_t ga = k * chunk_fam, gb = (uint32_t)std::min<uint64_t>((uint64_t)ga + chunk_fam, n_grp);
+          if (ga >= gb) break;
+          hip_check(hipStreamWaitEvent(s, fp.ev_chunk[k], 0), "wait");
+          if (S.build) launch_split_cols<160, 80>(S, pair_build, PS, ga, gb - ga); else launch_split_cols<0, 0>(S, pair_build, PS, ga, gb - ga);
+          // the chunk's EndDescs / record sizes / counters (a thread per family: waits on memory, few instructions) on the second
+          // stream, under the next chunk's column kernel
+          hip_check(hipEventRecord(fp.ev_cols[k], s), "event");
+          hip_check(hipStreamWaitEvent(fp.s2, fp.ev_cols[k], 0), "wait");
+          FastParams PF = P;
+          PF.group_list = nullptr; PF.g0 = ga;
+          FGX_LAUNCH(k_split_finish, dim3((gb - ga + 255) / 256), dim3(256), 0, fp.s2, PF, gb - ga);
+          if (paced && k + 2 < n_chunks) launch_parse(k + 2, dir_scan_bytes);
+        }
+      } else {
+        if (S.build) launch_split_cols<160, 80>(S, pair_build, PS, 0u, n_cur); else launch_split_cols<0, 0>(S, pair_build, PS, 0u, n_cur);
+        FastParams PF = P;                       // the families this (larger-slice) launch finished: the list it was given
+        PF.group_list = cur_list; PF.g0 = 0;
+        FGX_LAUNCH(k_split_finish, dim3((n_cur + 255) / 256), dim3(256), 0, s, PF, n_cur);
+      }
+      // (round 6: the route / big counters come along — after the LAST stage they are final, and two host synchronisations of their own go away)
+      unsigned long long h_cnt[MISC_SPLIT_WINDOW] = {};
+      hip_check(hipMemcpyAsync(h_cnt, misc + MISC_N_RETRY, sizeof(h_cnt), hipMemcpyDeviceToHost, s), "D2H");
+      split_counts_seen = true;
+      sync();
+      const uint32_t n_next = PS.retry ? (uint32_t)h_cnt[0] : 0u;
+      h_route_seen = (uint32_t)h_cnt[MISC_N_ROUTE - MISC_N_RETRY]; h_big_seen = (uint32_t)h_cnt[MISC_N_BIG - MISC_N_RETRY];
+      if (ci == 0) fp.last_first_stage_retries = n_next;
+      next_list(n_next);
+    }
+    hip_check(hipEventRecord(fp.ev_fin, fp.s2), "event");          // the per-chunk k_split_finish launches
+    join_s2(fp.ev_fin);
+    uint32_t n_route = h_route_seen;
+    if (!split_counts_seen) {
+      hip_check(hipMemcpyAsync(&n_route, cnt(MISC_N_ROUTE), 4, hipMemcpyDeviceToHost, s), "D2H");
+      sync();
+    }
+    cur_list = fp.d_route.as<uint32_t>(); n_cur = n_route; out_list = 0;
+    fp.last_routed = n_route;
+    if (ps.verbose) fprintf(stderr, "[fgx] split pipeline: %u families, %u routed to k_simplex_wave2\n", n_grp, n_route);
+  }
+  // QS, SS: the build with rows of 160 + 80 bytes as immediates, or 0, 0.  (round 5) `pair_build`: the packed pass for the families of its shape and, when
+  // PS.s2_partner announces it, run_cols for the rest as a second launch over the same families; (round 6) the later stages — the families that
+  // need larger LDS slices: ends of 9 .. 31 rows — always as the pair (their lists are mixed)
+  template <int QS, int SS> void launch_split_cols(const Slice& S, bool pair_build, FastParams& PS, uint32_t g_first, uint32_t count) {
+    PS.g0 = g_first;
+    const uint32_t wpb = std::min<uint32_t>(S.wpb, 65536u / S.bytes);   // wpb x slice within the 64 KiB requested for k_split_cols
+    const size_t lds = (size_t)wpb * S.bytes;
+    const dim3 grid((count + wpb - 1) / wpb), block(64 * wpb);
+    if (direct) FGX_LAUNCH(HIP_KERNEL_NAME(k_split_cols<QS, SS, 1, 0>), grid, block, lds, s, PS, count);
+    else if (!pair_build) FGX_LAUNCH(HIP_KERNEL_NAME(k_split_cols<QS, SS, 0, 0>), grid, block, lds, s, PS, count);
+    else {
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_split_cols<QS, SS, 0, 1>), grid, block, lds, s, PS, count);
+      if (PS.s2_partner) FGX_LAUNCH(HIP_KERNEL_NAME(k_split_cols<QS, SS, 0, 2>), grid, block, lds, s, PS, count);
+    }
+  }
+
+  // ---- split pipeline: the record kernel (k_split_parse) on the second stream ----
+  void prepare_parse() {   // its buffers, streams and parameters
+    fp.d_split_rec.reserve((size_t)n_rec * sizeof(SplitRec) + 64);
+    fp.d_split_fam.reserve((size_t)n_grp * sizeof(SplitFam) + 64);
+    if (!fp.s2) {
+      create_compute_stream(&fp.s2);
+      for (int i = 0; i < FastPath::MAX_CHUNKS; i++) { hip_check(hipEventCreateWithFlags(&fp.ev_chunk[i], hipEventDisableTiming), "hipEventCreate"); hip_check(hipEventCreateWithFlags(&fp.ev_cols[i], hipEventDisableTiming), "hipEventCreate"); }
+      hip_check(hipEventCreateWithFlags(&fp.ev_fin, hipEventDisableTiming), "hipEventCreate");
+      hip_check(hipEventCreateWithFlags(&fp.ev_sample, hipEventDisableTiming), "hipEventCreate");
+    }
+    memset(&PK, 0, sizeof(PK));
+    PK.blob = d_blob; PK.rec_off = d_rec_off; PK.rec_len = d_rec_len; PK.grp_first = d_grp_first; PK.blob_len = blob_len;
+    PK.min_reads = o.min_reads; PK.max_reads = o.max_reads; PK.overlap = o.overlapping_consensus;
+    PK.tag0 = o.tag[0]; PK.tag1 = o.tag[1]; PK.cell0 = o.cell_tag[0]; PK.cell1 = o.cell_tag[1];
+    PK.prefix_len = (uint32_t)c->prefix.size();
+    PK.split_rec = fp.d_split_rec.as<SplitRec>(); PK.split_fam = fp.d_split_fam.as<SplitFam>();
+  }
+  void fork_s2() {   // the second stream starts where this one is: the batch's buffers, the memsets
+    hip_check(hipEventRecord(fp.ev_chunk[FastPath::MAX_CHUNKS - 1], s), "event");
+    hip_check(hipStreamWaitEvent(fp.s2, fp.ev_chunk[FastPath::MAX_CHUNKS - 1], 0), "wait");
+  }
+  void launch_parse(uint32_t ci, size_t dir_scan_bytes = 0) {
+    const uint32_t ga = ci * chunk_fam, gb = std::min<uint64_t>((uint64_t)ga + chunk_fam, n_grp);
+    if (ga >= gb) return;
+    const uint64_t waves = ((uint64_t)(gb - ga) + fpw - 1) / fpw;
+    s2_busy = true;
+    FGX_LAUNCH(k_split_parse, dim3((uint32_t)((waves + 1) / 2)), dim3(128), 0, fp.s2, PK, ga, gb, fpw, (uint64_t*)nullptr, 3u, (uint4*)nullptr);
+    if (direct) {   // the chunk's record offsets: exclusive scan of the predicted family sizes, carried on from the chunk before
+      const DirSizeIn in(fp.d_dir_size.as<uint32_t>() + ga, DirCast());
+      hip_check(hipcub::DeviceScan::ExclusiveSum(fp.d_scan_tmp2.p, dir_scan_bytes, in, fp.d_dir_off.as<uint64_t>() + ga, (int)(gb - ga), fp.s2), "scan of the record sizes");
+      FGX_LAUNCH(k_dir_carry, dim3((gb - ga + 255) / 256), dim3(256), 0, fp.s2, fp.d_dir_off.as<uint64_t>() + ga, fp.d_dir_size.as<uint32_t>() + ga, gb - ga, fp.d_dir_base.as<uint64_t>() + ci);
+    }
+    hip_check(hipEventRecord(fp.ev_chunk[ci], fp.s2), "event");
+  }
+  // (round 6) The record kernel of the FIRST chunk starts before the column bounds are counted and scanned: it needs nothing of them, and the host
+  // waits for its first families anyway (their tile strides pick the column kernel's build).  Before, the second stream started behind
+  // k_col_bound + scan + a host synchronisation: 0.37 ms into the step.  Launched when the batch can take the split pipeline at all; should the count of
+  // small families then say otherwise, its descriptors are simply not used.
+  void parse_first_chunk_early() {
+    if (!(simplex_v2 && sw.split && !seg4 && !sw.direct && ps.early)) return;
+    prepare_parse();
+    fork_s2();
+    launch_parse(0);
+    early_parse = true;
+  }
+
+  // ---- k_simplex_seg<4> / <2> (4 / 2 families per wavefront, while the mean family fits a quarter / half of the wave's LDS) → k_simplex_wave2
+  //      (two-accumulator column loop, the families of the common record shape) over the growing slices.  What is outside their shape is
+  //      collected in `retry_old` and goes through the k_family_wave<0> launches ----
+  void wave2_chain() {
+    if (!fp.v2_attr_set) {
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_simplex_wave2);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 32768, k_simplex_seg<2>);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 32768, k_simplex_seg<4>);
+      fp.v2_attr_set = true;
+    }
+    P.w2_image = table_image<W2Lds>(fp.d_w2img, build_w2_image, "H2D w2 image");
+    P.fam_desc = fp.d_famdesc.as<uint4>();
+    std::vector<Slice> chain;   // (Slice.build: families per wavefront)
+    if (ps.seg && mean_span + (16 * 8 + 64) <= sw.seg_bytes / 4) chain.push_back({sw.seg_bytes, ps.seg_wpb, 4});
+    if (ps.seg && ps.seg2 && mean_span + (32 * 8 + 64) <= sw.seg_bytes / 2) chain.push_back({sw.seg_bytes, (uint32_t)WAVES_PER_BLOCK, 2});
+    // (workgroup-cooperative variants — four families' record phases on one wavefront, 11.9 ms; a producer / consumer pipeline in persistent workgroups,
+    // 19.3 ms — against 10.2 ms per 1 M depth-8 families here: the CU is fed by the number of independent wavefronts, not by lane utilisation.  HISTORY.md §4)
+    wave_slices(chain, ps.w2_wpb);
+    fp.d_retry_old.reserve((size_t)n_grp * 4);
+    const bool ran = n_cur != 0;
+    run_slices(chain, false, [&](const Slice& S, FastParams& PS) {
+      PS.retry_old = fp.d_retry_old.as<uint32_t>(); PS.n_retry_old = cnt(MISC_N_RETRY_OLD);
+      const uint32_t fpb = S.wpb * (uint32_t)S.build;      // families per workgroup
+      const dim3 grid((n_cur + fpb - 1) / fpb), block(64 * S.wpb);
+      const size_t lds = (size_t)S.wpb * S.bytes;
+      if (S.build == 4) FGX_LAUNCH(HIP_KERNEL_NAME(k_simplex_seg<4>), grid, block, lds, s, PS, n_cur);
+      else if (S.build == 2) FGX_LAUNCH(HIP_KERNEL_NAME(k_simplex_seg<2>), grid, block, lds, s, PS, n_cur);
+      else FGX_LAUNCH(k_simplex_wave2, grid, block, lds, s, PS, n_cur);
+    });
+    uint32_t n_old = 0;
+    if (ran) {   // (no kernel of the chain has run — the split pipeline kept every family —: nothing to read, no synchronisation)
+      hip_check(hipMemcpyAsync(&n_old, cnt(MISC_N_RETRY_OLD), 4, hipMemcpyDeviceToHost, s), "D2H");
+      sync();
+    }
+    cur_list = fp.d_retry_old.as<uint32_t>(); n_cur = n_old; out_list = 0;
+  }
+
+  // ---- k_family_wave: duplex, CODEC, simplex with --trim, and what k_simplex_wave2 left ----
+  void family_wave_stages() {
+    std::vector<Slice> st;
+    wave_slices(st, ps.fw_wpb);
+    run_slices(st, !(duplex || codec), [&](const Slice& S, FastParams& PS) {
+      const dim3 grid((n_cur + S.wpb - 1) / S.wpb), block(64 * S.wpb);
+      const size_t lds = (size_t)S.wpb * S.bytes;
+      if (codec) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<2>), grid, block, lds, s, PS, n_cur);
+      else if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1, 1>), grid, block, lds, s, PS, n_cur);
+      else if (duplex) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1>), grid, block, lds, s, PS, n_cur);
+      else FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<0>), grid, block, lds, s, PS, n_cur);
+    });
+    if (meth_dup) fp.last_meth_device = n_grp;
+  }
+
+  // ---- deep families: k_deep_parse + k_deep_cols (simplex_deep.inc) take the big list; what is outside their shape goes on to k_family ----
+  // One pass of the streaming kernels over a family list; returns how many families it handed on (to `out`).
+  // `size_class`: 0 = the wavefront-sized build of the record kernel (families of up to 64 records), 1 = two wavefronts (up to 128), 2 = four (up to DEEP_MAX)
+  uint32_t deep_pass(const uint32_t* list, uint32_t n_list, int size_class, uint32_t* out) {
+    fp.d_deep_sizes.reserve((size_t)n_list * 8 + 64); fp.d_deep_row0.reserve((size_t)n_list * 8 + 64);
+    FGX_LAUNCH(k_deep_sizes, dim3((n_list + 255) / 256), dim3(256), 0, s, list, n_list, d_grp_first, fp.d_deep_sizes.as<uint64_t>());
+    scan_u64(fp.d_deep_sizes.as<uint64_t>(), fp.d_deep_row0.as<uint64_t>(), n_list, "scan of the deep families' records");
+    uint64_t lastr[2] = {0, 0};
+    hip_check(hipMemcpyAsync(&lastr[0], fp.d_deep_row0.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&lastr[1], fp.d_deep_sizes.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    const uint64_t n_rows = lastr[0] + lastr[1];
+    if (n_rows > (uint64_t)n_rec) throw std::runtime_error("device pipeline: " + std::to_string(n_rows) + " rows for the streaming kernels, more than the batch has records");
+    fp.d_deep_rows.reserve((size_t)n_rows * sizeof(DeepRow) + 64); fp.d_deep_fams.reserve((size_t)n_list * sizeof(DeepFam) + 64);
+    hip_check(hipMemsetAsync(cnt(MISC_N_DEEP), 0, 4, s), "memset");
+    DeepParams DP;
+    DP.list = list; DP.n_list = n_list; DP.row0 = fp.d_deep_row0.as<uint64_t>();
+    DP.rows = fp.d_deep_rows.as<DeepRow>(); DP.fams = fp.d_deep_fams.as<DeepFam>(); DP.out_list = out; DP.n_out = cnt(MISC_N_DEEP);
+    FastParams PD = P;
+    PD.group_list = nullptr;
+    if (size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64>), dim3(n_list), dim3(64), 0, s, PD, DP);
+    else if (size_class == 1) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
+    else FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    if (meth_dev) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_cols<1>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
+    else FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_cols<0>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
+    uint32_t n_left = 0;
+    hip_check(hipMemcpyAsync(&n_left, cnt(MISC_N_DEEP), 4, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    return n_left;
+  }
+  void deep_families() {
+    if (!duplex && !codec) {
+      if (split_counts_seen && fp.last_routed == 0) n_big = h_big_seen;   // (no kernel after the split stages has run: what their last synchronisation read is final)
+      else {
+        hip_check(hipMemcpyAsync(&n_big, cnt(MISC_N_BIG), 4, hipMemcpyDeviceToHost, s), "D2H");
+        sync();
+      }
+    }
+    if (meth_dev) {
+      fp.d_big.reserve((size_t)n_grp * 4);
+      FGX_LAUNCH(k_iota, dim3((n_grp + 255) / 256), dim3(256), 0, s, fp.d_big.as<uint32_t>(), n_grp);
+      n_big = n_grp;
+    }
+    fp.last_big_families = n_big;
+    big_list = fp.d_big.as<uint32_t>();
+    if (!(n_big && (sw.deep || meth_dev) && !o.trim)) return;
+    P.s2_image = table_image<S2Image>(fp.d_s2img, build_s2_image, "H2D s2 image");   // (the column kernel's LDS tables: the split pipeline's image)
+    fp.d_deep_out.reserve((size_t)n_big * 4 + 64);
+    // Methylation-aware mode, every family: the wavefront-sized build of the record kernel first; what neither build takes is on the deferred list (the
+    // general path knows the mode).  Else (round 6) two wavefronts per family first: a family of 65 .. 128 records — every deep family of a 2 .. 50-pair
+    // long tail — kept a quarter to a half of the 256 threads of the large build busy in the record kernel.  What has more records goes on to the large build.
+    const uint32_t n_more = deep_pass(fp.d_big.as<uint32_t>(), n_big, meth_dev ? 0 : 1, fp.d_deep_out.as<uint32_t>());
+    uint32_t n_left = 0;
+    big_list = fp.d_deep_out.as<uint32_t>();
+    if (n_more) {
+      fp.d_deep_out2.reserve((size_t)n_more * 4 + 64);
+      n_left = deep_pass(fp.d_deep_out.as<uint32_t>(), n_more, 2, fp.d_deep_out2.as<uint32_t>());
+      big_list = fp.d_deep_out2.as<uint32_t>();
+    }
+    fp.last_deep_families = meth_dev ? n_big : n_big - n_left;
+    if (meth_dev) fp.last_meth_device = n_grp;
+    n_big = meth_dev ? 0u : n_left;   // (what is not the kernels' shape: k_family)
+  }
+
+  // ---- k_family, one workgroup per family: more bytes than the largest slice (what the chain left), then more than 64 records (what the
+  //      streaming kernels left of the list the first kernels filled) ----
+  void workgroup_families() {
+    for (int pass = 0; pass < 2 && !duplex && !codec; pass++) {
+      const uint32_t n = pass == 0 ? n_cur : n_big;
+      if (!n) continue;
+      FastParams P2 = P;
+      P2.group_list = pass == 0 ? cur_list : big_list; P2.retry = nullptr; P2.n_retry = nullptr;
+      if (sw.lds_tile_large) { fp.lds_tile_bytes_large = sw.lds_tile_large; P2.lds_tile_bytes = fp.lds_tile_bytes_large; }
+      FGX_LDS_ATTR((int)fp.lds_tile_bytes_large, k_family);
+      FGX_LAUNCH(k_family, dim3(n), dim3(NT), fp.lds_tile_bytes_large, s, P2);
+    }
+  }
+
+  // ---- k_call_full: the dense pass over the append lists.  RUN_AGAIN_LARGER_POOL: every list was full, the batch again with twice the room ----
+  int call_full() {
+    std::vector<uint32_t> counts(N_LISTS);
+    hip_check(hipMemcpyAsync(counts.data(), fp.d_full_count.p, (size_t)N_LISTS * 4, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    uint32_t mx = 0, mn = 0xFFFFFFFFu;
+    for (uint32_t v : counts) { uint32_t vv = v < full_cap ? v : full_cap; mx = vv > mx ? vv : mx; mn = v < mn ? v : mn; n_full += vv; }
+    if (mn >= full_cap && fp.pool_div > 1) {
+      // every list is full: some family found no room (and was deferred).  Twice the room, if the device has it, and the batch again.
+      size_t free_b = 0, total_b = 0;
+      (void)hipMemGetInfo(&free_b, &total_b);
+      const uint64_t want = (col_cap / (fp.pool_div / 2) + (uint64_t)N_LISTS * fp.pool_slack) * sizeof(FullItem);
+      if (want < (uint64_t)free_b + (uint64_t)fp.d_full_items.cap) {
+        fp.pool_div /= 2;
+        if (ps.verbose) fprintf(stderr, "[fgx] call_full pool exhausted: the batch again with 1/%u of the column bound\n", fp.pool_div);
+        return FastPath::RUN_AGAIN_LARGER_POOL;
+      }
+    }
+    if (mx) {
+      FullParams F;
+      memset(&F, 0, sizeof(F));
+      F.items = fp.d_full_items.as<FullItem>(); F.count = fp.d_full_count.as<uint32_t>(); F.cap = full_cap;
+      F.T = P.T; F.TU = P.TU; F.min_reads = P.min_reads; F.min_cons_bq = P.min_cons_bq;
+      F.col_code = P.col_code; F.col_qual = P.col_qual; F.col_err = P.col_err;
+      F.col_depth = P.col_depth; F.min_input_bq = P.min_input_bq;
+      F.out = P.out; F.slot_desc = P.slot_desc; F.slot_err = P.slot_err; F.rg_len = P.rg_len; F.per_base_tags = P.per_base_tags;
+      F.rx_base = fp.d_ends.as<char>() + (duplex ? offsetof(DuplexDesc, rx) : codec ? offsetof(CodecDesc, rx) : offsetof(EndDesc, rx));
+      F.rx_stride = duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc);
+      FGX_LAUNCH(k_call_full, dim3((mx + 255) / 256, N_LISTS), dim3(256), 0, s, F);
+    }
+    // the methylation tags' share of the record sizes: the consensus bases are final now
+    if (meth_dev) FGX_LAUNCH(k_meth_sizes, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, fp.d_mslot.as<MethSlot>());
+    if (meth_dup) FGX_LAUNCH(k_duplex_meth_sizes, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, fp.d_mslot.as<DuplexMethSlot>());
+    return 0;
+  }
+
+  // ---- direct records: cE of the records whose columns had errors; did every prediction hold; is there anything to merge? ----
+  int check_direct() {
+    FGX_LAUNCH(k_fix_ce, dim3((n_slots + 255) / 256), dim3(256), 0, s, fp.d_slot_desc.as<SlotDesc>(), fp.d_slot_err.as<uint32_t>(), n_slots, fp.d_out.as<uint8_t>(), P.rg_len);
+    unsigned long long h_flags = 0, h_def = 0, h_route = 0;
+    hip_check(hipMemcpyAsync(&h_flags, misc + MISC_DIR_FLAGS, 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&h_def, misc + MISC_N_DEFERRED, 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&h_route, misc + MISC_N_ROUTE, 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&dir_total, fp.d_dir_base.as<uint64_t>() + fp.dir_chunks_run, 8, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    if ((uint32_t)h_flags != 0) {          // a family's records are not what k_split_parse predicted: nothing of the batch can be trusted to be in place
+      fprintf(stderr, "[fgx] direct records: %u families differ in size from the prediction; this caller goes back to the column scratch (please report)\n", (uint32_t)h_flags);
+      fp.direct_off = true;
+      return FastPath::RUN_AGAIN_LARGER_POOL;
+    }
+    if ((uint32_t)(h_flags >> 32) != 0) {  // more record bytes than the first estimate of the room: the exact amount is known now
+      fp.dir_cap_min = dir_total + dir_total / 16 + 4096;
+      if (ps.verbose) fprintf(stderr, "[fgx] direct records: the batch needs %llu bytes of output, %llu were at hand: again\n", (unsigned long long)dir_total, (unsigned long long)dir_cap);
+      return FastPath::RUN_AGAIN_LARGER_POOL;
+    }
+    dir_routed = (uint32_t)h_route;
+    dir_pure = dir_routed == 0 && (uint32_t)h_def == 0;
+    fp.last_direct = dir_pure ? 1 : 2;
+    if (ps.verbose) fprintf(stderr, "[fgx] direct records: %llu bytes in place, %u families left the split pipeline, %u deferred\n", (unsigned long long)dir_total, dir_routed, (uint32_t)h_def);
+    return 0;
+  }
+
+  // ---- where the records go: the scan of their sizes (its last element is the total: d_sizes[n_slots] is 0), the output buffer ----
+  void place_records() {
+    hip_check(hipEventRecord(fp.ev[1], s), "event");
+    out_len = dir_total;
+    out_ptr = fp.d_out.as<uint8_t>();
+    if (dir_pure) return;
+    scan_u64(fp.d_sizes.as<uint64_t>(), fp.d_offsets.as<uint64_t>(), n_slots + 1, "scan");
+    uint64_t out_total = 0;
+    hip_check(hipMemcpyAsync(&out_total, fp.d_offsets.as<uint64_t>() + n_slots, 8, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    out_len = out_total;
+    if (out_len > (1ull << 40)) throw std::runtime_error("device pipeline: the scan of the record sizes gives " + std::to_string(out_len) + " bytes of output (a record size is corrupt)");
+    if (direct) { fp.d_out2.reserve(out_len + 16); out_ptr = fp.d_out2.as<uint8_t>(); }   // the merged stream: d_out holds the directly written records
+    else { fp.d_out.reserve(out_len + 16); out_ptr = fp.d_out.as<uint8_t>(); }
+  }
+
+  // what the three record writers' parameters share
+  template <class EP, class Desc> void emit_params(EP& E, const Desc* ends, uint8_t* out) const {
+    memset(&E, 0, sizeof(E));
+    E.blob = d_blob; E.rec_off = d_rec_off; E.ends = ends; E.out_off = fp.d_offsets.as<uint64_t>(); E.out = out;
+    E.slot_end = n_slots;
+    E.col_code = P.col_code; E.col_qual = P.col_qual; E.col_err = P.col_err;
+    E.prefix = fp.d_strings.as<char>(); E.prefix_len = P.prefix_len; E.rg = fp.d_strings.as<char>() + P.prefix_len; E.rg_len = P.rg_len;
+    E.per_base_tags = P.per_base_tags; E.cell0 = P.cell0; E.cell1 = P.cell1;
+  }
+  // ---- the record writers, the counters, the result ----
+  // (round 6) duplex / CODEC: the per-field record writer (k_emit_duplex / k_emit_codec: any length, any tag size) used to run over EVERY slot behind the fast
+  // writer and find nothing to do (0.97 / 0.33 ms per step of wavefronts that load a descriptor and leave); a counting kernel (a thread per slot) now says
+  // how many records the fast writer refuses, and the per-field kernel is launched — after the batch's last synchronisation — only when there are any
+  void write_records() {
+    hip_check(hipEventRecord(fp.ev[2], s), "event");
+    const dim3 per_slot((n_slots + 255) / 256), wave_per_slot((n_slots + 3) / 4), wave_per_family((n_grp + 3) / 4);
+    DuplexEmitParams DE;
+    CodecEmitParams CE;
+    if (codec) {
+      emit_params(CE, fp.d_ends.as<CodecDesc>(), fp.d_out.as<uint8_t>());
+      CE.col_depth = P.col_depth;
+      CE.has_outer = o.codec_has_outer_bases_qual; CE.outer_qual = o.codec_outer_bases_qual; CE.outer_len = o.codec_outer_bases_length;
+      CE.has_ss = o.codec_has_single_strand_qual; CE.ss_qual = o.codec_single_strand_qual;
+      CE.stats = fp.d_statslots.as<unsigned long long>();
+      CE.n_slow = cnt(MISC_N_SLOW);
+      FGX_LAUNCH(k_count_slow_codec, per_slot, dim3(256), 0, s, CE.ends, 0u, n_slots, CE.prefix_len, CE.rg_len, CE.n_slow);
+      FGX_LAUNCH(k_emit_codec_fast, wave_per_slot, dim3(256), 0, s, CE);
+    } else if (duplex) {
+      emit_params(DE, fp.d_ends.as<DuplexDesc>(), fp.d_out.as<uint8_t>());
+      DE.col_obs = P.col_obs;
+      DE.n_slow = cnt(MISC_N_SLOW);
+      DE.meth_flag = P.meth_flag;
+      FGX_LAUNCH(k_count_slow_duplex, per_slot, dim3(256), 0, s, DE.ends, 0u, n_slots, DE.prefix_len, DE.rg_len, DE.n_slow);
+      if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<1>), wave_per_slot, dim3(256), 0, s, DE);
+      else FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<0>), wave_per_slot, dim3(256), 0, s, DE);
+    } else if (!direct || !dir_pure) {
+      EmitParams E;
+      emit_params(E, fp.d_ends.as<EndDesc>(), out_ptr);
+      E.col_depth = P.col_depth; E.tag0 = P.tag0; E.tag1 = P.tag1;
+      if (!direct) FGX_LAUNCH(k_emit, wave_per_family, dim3(256), 0, s, E);   // one wavefront per family (slots 3g .. 3g + 2)
+      else {
+        // the merge: the families that left the split pipeline are written by k_emit from their descriptors, the directly written ones move
+        // to their place in the final stream
+        if (dir_routed) {
+          E.fam_list = fp.d_route.as<uint32_t>(); E.n_fam = dir_routed;
+          FGX_LAUNCH(k_emit, dim3((dir_routed + 3) / 4), dim3(256), 0, s, E);
+        }
+        FGX_LAUNCH(k_dir_copy, wave_per_family, dim3(256), 0, s, fp.d_split_out.as<SplitOut>(), fp.d_dir_off.as<uint64_t>(), fp.d_offsets.as<uint64_t>(),
+                   fp.d_sizes.as<uint64_t>(), fp.d_out.as<uint8_t>(), out_ptr, n_grp);
+      }
+    }
+    if (meth_dev) FGX_LAUNCH(k_meth_tail, wave_per_slot, dim3(256), 0, s, P, n_slots, fp.d_mslot.as<MethSlot>(), fp.d_offsets.as<uint64_t>(), out_ptr);
+    if (meth_dup) FGX_LAUNCH(k_duplex_meth_tail, wave_per_slot, dim3(256), 0, s, P, n_slots, fp.d_mslot.as<DuplexMethSlot>(), fp.d_offsets.as<uint64_t>(), out_ptr);
+    hip_check(hipEventRecord(fp.ev[3], s), "event");
+    hip_check(hipEventRecord(c->ev1, s), "event");
+    unsigned long long h_misc[MISC_READ_BACK];
+    auto read_counters = [&] {
+      FGX_LAUNCH(k_reduce_stats, dim3(1), dim3(64), 0, s, fp.d_statslots.as<unsigned long long>(), misc);
+      hip_check(hipMemcpyAsync(h_misc, misc, sizeof(h_misc), hipMemcpyDeviceToHost, s), "D2H");
+      sync();
+    };
+    read_counters();
+    if ((duplex || codec) && (uint32_t)h_misc[MISC_N_SLOW] != 0) {     // records the fast writer left: the per-field kernel, then the counters again (the CODEC writer counts bases)
+      if (codec) FGX_LAUNCH(k_emit_codec, wave_per_slot, dim3(256), 0, s, CE);
+      else if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<1>), wave_per_slot, dim3(256), 0, s, DE);
+      else FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<0>), wave_per_slot, dim3(256), 0, s, DE);
+      read_counters();
+    }
+    float ms = 0, msf = 0, mse = 0;
+    hip_check(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
+    hip_check(hipEventElapsedTime(&msf, fp.ev[0], fp.ev[1]), "elapsed");
+    hip_check(hipEventElapsedTime(&mse, fp.ev[2], fp.ev[3]), "elapsed");
+    res->d_out = out_ptr;
+    res->out_len = out_len;
+    res->count = h_misc[MISC_STATS + 1];   // every consensus read of a fast-path family is one record
+    for (int i = 0; i < FGX_STATS_LEN; i++) res->stats[i] = h_misc[MISC_STATS + i];
+    res->n_deferred = (uint32_t)(h_misc[MISC_N_DEFERRED] & 0xFFFFFFFFull);
+    res->d_deferred = fp.d_deferred.as<uint32_t>();
+    res->d_out_off = fp.d_offsets.as<uint64_t>();
+    res->d_slot_size = fp.d_sizes.as<uint64_t>();
+    res->n_slots = n_slots;
+    res->ms_kernels = ms; res->ms_k_family = msf; res->ms_k_emit = mse;
+    fp.last_packed_families = h_misc[MISC_BUILD_FAMILIES]; fp.last_classic_families = h_misc[MISC_BUILD_FAMILIES + 1];
+    res->cols_used = h_misc[MISC_COLS_USED];
+    res->full_items = n_full;
+  }
+};
+
+// One batch through the launch chain: the stages in the order they enqueue.  RUN_AGAIN_LARGER_POOL: FastPath::run calls again.
+int run_once(FastPath& fp, fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, const uint64_t* d_rec_off, const uint32_t* d_rec_len, uint32_t n_rec,
+             const uint32_t* d_grp_first, uint32_t n_grp, FastResult* res) {
+  memset(res, 0, sizeof(*res));
+  fp.last_launches = 0; fp.last_host_syncs = 0;
+  if (n_grp == 0) return 0;
+  static const ProcessSwitches ps{};
+  Batch b{fp, c, d_blob, blob_len, d_rec_off, d_rec_len, n_rec, d_grp_first, n_grp, res, ps};
+  b.set_up();
+  b.parse_first_chunk_early();
+  b.bound_columns();
+  b.fill_params();
+  if (b.use_split) b.split_pipeline();
+  if (b.simplex_v2) b.wave2_chain();
+  b.family_wave_stages();
+  b.deep_families();
+  b.workgroup_families();
+  if (const int rc = b.call_full()) return rc;
+  if (b.direct) if (const int rc = b.check_direct()) return rc;
+  b.place_records();
+  b.write_records();
+  return 0;
+}
+
+}  // namespace
+
 // The columns whose call needs the log-sum-exp chain wait in append lists for k_call_full.  Their room is a fraction of the column
 // bound (1/8: clean libraries need under 1 %); when a batch fills EVERY list — a noisy library: a few per cent of disagreeing bases
 // at depth 8 — the batch is run again with twice the room (and the caller keeps the larger fraction for its next batches) instead
@@ -4019,7 +4878,7 @@ int FastPath::run(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, const
     pool_init = true;
   }
   for (;;) {
-    const int rc = run_once(c, d_blob, blob_len, d_rec_off, d_rec_len, n_rec, d_grp_first, n_grp, res);
+    const int rc = run_once(*this, c, d_blob, blob_len, d_rec_off, d_rec_len, n_rec, d_grp_first, n_grp, res);
     if (rc != RUN_AGAIN_LARGER_POOL) {
       if (const char* e = fgx_knob("FGX_S2_DEBUG")) if (atoi(e)) {   // (development: the packed pass's counters, cumulative over the process)
         uint32_t h[64];
@@ -4031,867 +4890,6 @@ int FastPath::run(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, const
       return rc;
     }
   }
-}
-
-int FastPath::run_once(fgx_caller* c, const uint8_t* d_blob, uint64_t blob_len, const uint64_t* d_rec_off, const uint32_t* d_rec_len,
-                       uint32_t n_rec, const uint32_t* d_grp_first, uint32_t n_grp, FastResult* res) {
-  const fgx_options& o = c->opt;
-  const bool duplex = o.caller_kind == FGX_CALLER_DUPLEX, codec = o.caller_kind == FGX_CALLER_CODEC;
-  hipStream_t s = c->stream;
-  memset(res, 0, sizeof(*res));
-  last_launches = 0; last_host_syncs = 0;
-  if (n_grp == 0) return 0;
-  const uint32_t n_slots = 3 * n_grp;   // simplex: Fragment, R1, R2 of each family; duplex: slot 0 unused, R1, R2
-  d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
-  d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
-  d_offsets.reserve(((size_t)n_slots + 1) * 8);
-  d_deferred.reserve((size_t)n_grp * 4);
-  // misc: [0..28) stats, [28] col_cursor, [29] n_deferred (u32 in low half), [30] valid count
-  d_misc.reserve(48 * 8);   // ... [31] n_retry, [32] n_retry_old (k_simplex_wave2 → k_family_wave<0>); [40 .. 44) diagnostics (k_reduce_stats)
-  hip_check(hipMemsetAsync(d_misc.p, 0, 48 * 8, s), "memset");
-  // strings: prefix | rg
-  std::string strs = c->prefix + c->rg;
-  d_strings.reserve(strs.size() + 16);
-  if (!strs.empty()) hip_check(hipMemcpyAsync(d_strings.p, strs.data(), strs.size(), hipMemcpyHostToDevice, s), "H2D strings");
-  // column scratch: deterministic per-family slots from an exclusive scan of the column bound
-  (void)n_rec;
-  for (int i = 0; i < 4; i++) if (!ev[i]) hip_check(hipEventCreate(&ev[i]), "hipEventCreate");
-  unsigned long long* misc = d_misc.as<unsigned long long>();
-  d_bound.reserve(((size_t)n_grp + 1) * 8); d_colbase.reserve(((size_t)n_grp + 1) * 8);
-  d_statslots.reserve((size_t)STAT_SLOTS * 32 * 8);
-  hip_check(hipMemsetAsync(d_statslots.p, 0, (size_t)STAT_SLOTS * 32 * 8, s), "memset");
-  d_famdesc.reserve((size_t)n_grp * 16);
-  hip_check(hipEventRecord(c->ev0, s), "event");
-  hip_check(hipEventRecord(ev[0], s), "event");   // the family stage: record kernel / column bound, scan, family kernels, k_call_full
-  // Simplex without --trim: which head of the launch chain?  Shallow families (the mean family fits a quarter of a wave's LDS
-  // slice) start at k_simplex_seg<4>; everything else at the split pipeline (k_split_parse + k_split_cols, simplex_split.inc),
-  // whose record kernel also leaves what k_col_bound would (column bound, byte-span descriptor).
-  static const bool use_v2 = [] { const char* e = fgx_knob("FGX_V2"); return !(e && e[0] == '0'); }();
-  static const bool use_seg = [] { const char* e = fgx_knob("FGX_SEG"); return !(e && e[0] == '0'); }();
-  const bool use_split_env = [] { const char* e = getenv("FGX_SPLIT"); return !(e && e[0] == '0'); }();   // (read per batch: tests switch it inside one process)
-  uint32_t seg_bytes = 11776;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
-  if (const char* e = fgx_knob("FGX_SEG_BYTES")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 4096 && v <= 32768) seg_bytes = v & ~63u; }
-  const double mean_span = (double)blob_len / (double)n_grp + 48.0;   // mean bytes of a family + alignment / read-ahead slack
-  // Methylation-aware mode (simplex, a reference set, no --trim): the streaming kernels of simplex_deep.inc are the whole pipeline — every
-  // family on their list, the reference lookup / counts / normalisation in k_deep_cols<1>, MM / ML / cu / ct behind the standard record
-  // (k_meth_sizes, k_meth_tail); a family outside their shape is deferred to the general path, which knows the mode.
-  const bool meth_dev = !duplex && !codec && !o.trim && o.methylation_mode != FGX_METHYLATION_DISABLED && c->genome != nullptr;
-  // The duplex caller in the mode (a reference set, no --trim): the wavefront kernel's <1, 1> build annotates and normalises the four read sets of a
-  // molecule in its column loops, the record writers' <1> builds apply the conversion-artifact rule, am/au/at, bm/bu/bt, MM/ML/cu/ct follow RX
-  // (duplex_meth.inc).  A caller with the mode off launches the builds it always did.
-  const bool meth_dup = duplex && !o.trim && o.methylation_mode != FGX_METHYLATION_DISABLED && c->genome != nullptr;
-  last_meth_device = 0;
-  const bool simplex_v2 = !duplex && !codec && !o.trim && use_v2 && !meth_dev;
-  const bool seg4 = simplex_v2 && use_seg && mean_span + (16 * 8 + 64) <= seg_bytes / 4;
-  // the split pipeline's geometry: families per wavefront of the record kernel (as many as fill its 64 lanes on average), chunks, families per chunk
-  const double mean_recs = (double)n_rec / (double)n_grp;
-  auto split_geometry = [&](uint32_t& fpw, uint32_t& n_chunks, uint32_t& chunk_fam_raw, uint32_t& chunk_fam) {
-    fpw = mean_recs >= 1.0 ? (uint32_t)(64.0 / mean_recs) : 16u;
-    fpw = fpw < 1u ? 1u : fpw > 16u ? 16u : fpw;
-    if (const char* e = fgx_knob("FGX_SPLIT_FPW")) { const int v = atoi(e); if (v >= 1 && v <= 32) fpw = (uint32_t)v; }   // (measurement knob)
-    static const int chunks_env = [] { const char* e = getenv("FGX_SPLIT_CHUNKS"); return e ? atoi(e) : 0; }();      // (measurement knob)
-    // chunks of at least ~150 000 families (a column kernel of 37 500 workgroups: 20 rounds of the chip's resident workgroups, so that its tail — the
-    // last round runs with a part of the chip — stays a few per cent), eight at most: one rank's share of an 8-way strong-scaling run (625 000
-    // families) took 8 chunks of 78 000 until round 6 and spent a third of its step in launch gaps and kernel tails (bench.py share_of_8)
-    n_chunks = chunks_env >= 1 ? (uint32_t)chunks_env : std::min<uint32_t>(8u, std::max<uint32_t>(1u, n_grp / 150000u));
-    if (n_chunks > (uint32_t)MAX_CHUNKS - 1) n_chunks = MAX_CHUNKS - 1;   // (the last event marks where the second stream starts)
-    chunk_fam_raw = (n_grp + n_chunks - 1) / n_chunks;
-    chunk_fam = ((chunk_fam_raw + 4 * fpw - 1) / (4 * fpw)) * (4 * fpw);      // whole workgroups of both kernels per chunk
-  };
-  auto split_streams = [&]() {
-    if (!s2) { create_compute_stream(&s2); for (int i = 0; i < MAX_CHUNKS; i++) { hip_check(hipEventCreateWithFlags(&ev_chunk[i], hipEventDisableTiming), "hipEventCreate"); hip_check(hipEventCreateWithFlags(&ev_cols[i], hipEventDisableTiming), "hipEventCreate"); } hip_check(hipEventCreateWithFlags(&ev_fin, hipEventDisableTiming), "hipEventCreate"); hip_check(hipEventCreateWithFlags(&ev_sample, hipEventDisableTiming), "hipEventCreate"); }
-  };
-  auto split_parse_params = [&](FastParams& PK) {
-    memset(&PK, 0, sizeof(PK));
-    PK.blob = d_blob; PK.rec_off = d_rec_off; PK.rec_len = d_rec_len; PK.grp_first = d_grp_first; PK.blob_len = blob_len;
-    PK.min_reads = o.min_reads; PK.max_reads = o.max_reads; PK.overlap = o.overlapping_consensus;
-    PK.tag0 = o.tag[0]; PK.tag1 = o.tag[1]; PK.cell0 = o.cell_tag[0]; PK.cell1 = o.cell_tag[1];
-    PK.prefix_len = (uint32_t)c->prefix.size();
-    PK.split_rec = d_split_rec.as<SplitRec>(); PK.split_fam = d_split_fam.as<SplitFam>();
-  };
-  // (round 6) The record kernel of the FIRST chunk starts before the column bounds are counted and scanned: it needs nothing of them, and the host
-  // waits for its first families anyway (their tile strides pick the column kernel's build).  Before, the second stream started behind
-  // k_col_bound + scan + a host synchronisation: 0.37 ms into the step.  Launched when the batch can take the split pipeline at all; should the count of
-  // small families then say otherwise (below), its descriptors are simply not used.
-  bool early_parse = false;
-  {
-    const bool direct_env0 = [] { const char* e = getenv("FGX_DIRECT"); return e && e[0] == '1'; }();
-    static const bool early_env = [] { const char* e = fgx_knob("FGX_S2_EARLY"); return !(e && e[0] == '0'); }();      // (measurement knob)
-    if (simplex_v2 && use_split_env && !seg4 && !direct_env0 && early_env) {
-      d_split_rec.reserve((size_t)n_rec * sizeof(SplitRec) + 64);
-      d_split_fam.reserve((size_t)n_grp * sizeof(SplitFam) + 64);
-      split_streams();
-      uint32_t fpw, n_chunks, chunk_fam_raw, chunk_fam;
-      split_geometry(fpw, n_chunks, chunk_fam_raw, chunk_fam);
-      FastParams PK;
-      split_parse_params(PK);
-      hip_check(hipEventRecord(ev_chunk[MAX_CHUNKS - 1], s), "event");      // (behind what the stream holds: the batch's buffers, the memsets)
-      hip_check(hipStreamWaitEvent(s2, ev_chunk[MAX_CHUNKS - 1], 0), "wait");
-      const uint32_t gb = (uint32_t)std::min<uint64_t>(chunk_fam, n_grp);
-      const uint64_t waves = ((uint64_t)gb + fpw - 1) / fpw;
-      do { last_launches++; hipLaunchKernelGGL(k_split_parse, dim3((uint32_t)((waves + 1) / 2)), dim3(128), 0, s2, PK, 0u, gb, fpw, (uint64_t*)nullptr, 3u, (uint4*)nullptr); } while (0);
-      hip_check(hipGetLastError(), "k_split_parse launch (first chunk, early)");
-      hip_check(hipEventRecord(ev_chunk[0], s2), "event");
-      early_parse = true;
-    }
-  }
-  do { last_launches++; hipLaunchKernelGGL(k_col_bound, dim3((n_grp + 1023) / 1024), dim3(1024), 0, s, d_grp_first, d_rec_len, d_rec_off, n_grp, d_bound.as<uint64_t>(), duplex ? 4u : codec ? 2u : 3u,
-                     d_famdesc.as<uint4>(), misc + 35, d_sizes.as<uint64_t>() + n_slots); } while (0);
-  {
-    size_t tb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_bound.as<uint64_t>(), d_colbase.as<uint64_t>(), (int)n_grp + 1, s);
-    d_scan_tmp.reserve(tb);
-    hip_check(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tb, d_bound.as<uint64_t>(), d_colbase.as<uint64_t>(), (int)n_grp + 1, s), "scan bound");
-  }
-  // (round 6: every small device-to-host copy costs the stream ~25 us, timeline of the 625 000-family step — so the total is the scan's own last element)
-  uint64_t col_total = 0;
-  hip_check(hipMemcpyAsync(&col_total, d_colbase.as<uint64_t>() + n_grp, 8, hipMemcpyDeviceToHost, s), "D2H");
-  unsigned long long small_recs = 0;
-  hip_check(hipMemcpyAsync(&small_recs, misc + 35, 8, hipMemcpyDeviceToHost, s), "D2H");
-  FGX_SYNC(s);
-  // The split pipeline is the faster head for every family it keeps (depth 8: 25.7 against 37 ms per 5 M families) — since round 4 that is
-  // every family of up to 64 records in the common shape (an end of more than 16 reads sends its disagreeing columns to k_call_full as
-  // several items); larger families it only measures and hands to k_family.  Split when at least half of the reads sit in families of
-  // at most 64 records (FGX_SPLIT=0 / 2: never / always).
-  const int split_mode = [] { const char* e = getenv("FGX_SPLIT"); return e ? atoi(e) : 1; }();
-  const bool use_split = simplex_v2 && use_split_env && !seg4 && (split_mode == 2 || (double)small_recs >= 0.5 * (double)n_rec);
-  // Direct records (fastpath.h): the split pipeline's column kernel writes the consensus records itself (FGX_DIRECT=1).  Byte-identical on
-  // the GPU (tools/direct_check.py, tests/test_gpu_direct_records.py), but NOT the default: measured on 5 M depth-8 families the column kernel
-  // pays for the emission what k_emit cost as a kernel of its own (k_split_cols 2.82 -> 3.82 ms per chunk, k_split_parse 0.94 -> 1.41 ms with the
-  // size prediction; step 33.7 -> 40.2 ms with the merge, ~34 ms without: profiles/r04_experiments.md) — vector-instruction issue is what the
-  // stage is short of, and the record's constant bytes cost as many instructions written from here as from there.
-  const bool direct_env = [] { const char* e = getenv("FGX_DIRECT"); return e && e[0] == '1'; }();   // (read per batch: tools/direct_check.py switches it between two runs of one process)
-  const bool direct = use_split && direct_env && !direct_off && !meth_dev;
-  last_direct = 0;
-  if (early_parse && !use_split) hip_check(hipStreamWaitEvent(s, ev_chunk[0], 0), "wait");   // (its descriptors are not used; nothing of this batch may still run when the call returns)
-  last_routed = 0; last_big_families = 0; last_deep_families = 0; last_packed_families = 0; last_classic_families = 0; last_split_build = 0; last_first_stage_retries = 0;
-  uint64_t col_cap = col_total + 64;
-  uint64_t dir_cap = 0;
-  if (direct) {
-    // room for the records: 6 bytes per column of the (generous) column bound covers sequence + qualities + cd + ce twice over for
-    // simulate-shaped reads; names and tags come on top.  A batch that needs more says so (dir_flags[1]) and runs again with what it asked for.
-    dir_cap = std::max<uint64_t>(col_cap * 6 + (uint64_t)n_slots * 64 + 4096, dir_cap_min);
-    d_out.reserve(dir_cap + 64);
-    d_dir_size.reserve((size_t)n_grp * 4 + 64); d_dir_off.reserve((size_t)n_grp * 8 + 64); d_dir_base.reserve((MAX_CHUNKS + 2) * 8);
-    d_slot_desc.reserve((size_t)n_slots * sizeof(SlotDesc)); d_slot_err.reserve((size_t)n_slots * 4);
-    hip_check(hipMemsetAsync(d_dir_size.p, 0, (size_t)n_grp * 4, s), "memset");
-    hip_check(hipMemsetAsync(d_dir_base.p, 0, (MAX_CHUNKS + 2) * 8, s), "memset");
-    hip_check(hipMemsetAsync(d_slot_err.p, 0, (size_t)n_slots * 4, s), "memset");
-    hip_check(hipMemsetAsync(d_sizes.p, 0, ((size_t)n_slots + 1) * 8, s), "memset");
-  }
-  d_code.reserve(col_cap + 64); d_qual.reserve(col_cap + 64); d_err.reserve(col_cap * 2 + 64);   // (+ slack: k_emit reads whole dwords)
-  if (meth_dev || meth_dup) {
-    d_mflag.reserve(col_cap + 64); d_mu.reserve(col_cap * 2 + 64); d_mt.reserve(col_cap * 2 + 64);
-    d_mslot.reserve((size_t)n_slots * (meth_dup ? sizeof(DuplexMethSlot) : sizeof(MethSlot)) + 64);
-  }
-  if (duplex) d_obs.reserve(col_cap * 4); else d_depth.reserve(col_cap * 2 + 64);
-
-  FastParams P;
-  memset(&P, 0, sizeof(P));
-  P.blob = d_blob; P.rec_off = d_rec_off; P.rec_len = d_rec_len; P.grp_first = d_grp_first;
-  P.blob_len = blob_len;
-  P.g0 = 0;
-  P.T = c->d_tables.as<DeviceTables>(); P.TU = c->d_umi_tables.as<DeviceTables>();
-  if (!d_fwimg.p) {   // the tables of a caller never change: one image per FastPath (k_family_wave's LDS block)
-    FwLds* img = new FwLds;
-    build_fw_image(*img, c->h_tables.t);
-    d_fwimg.reserve(sizeof(FwLds));
-    hip_check(hipMemcpyAsync(d_fwimg.p, img, sizeof(FwLds), hipMemcpyHostToDevice, s), "H2D fw image");
-    FGX_SYNC(s);
-    delete img;
-  }
-  P.fw_image = d_fwimg.p;
-  P.min_reads = o.min_reads; P.max_reads = o.max_reads;
-  P.min_input_bq = o.min_input_base_quality; P.min_cons_bq = o.min_consensus_base_quality;
-  {   // k_split_cols's sum-free observation step: from how many agreeing observations a column is the cap whatever their qualities (gate_core.h)
-    static const int nosum_env = [] { const char* e = fgx_knob("FGX_S2_NOSUM"); return e ? atoi(e) : 1; }();      // (measurement knob: 0 = every end through the f32 sums)
-    static const int packed_env = [] { const char* e = getenv("FGX_S2_PACKED"); return e ? atoi(e) : 1; }();   // (measurement knob: 0 = the 64-column passes only)
-    static const int s2dbg_env = [] { const char* e = fgx_knob("FGX_S2_DEBUG"); return e ? atoi(e) : 0; }();
-    P.s2_packed = (packed_env ? 1u : 0u) | ((packed_env && s2dbg_env) ? 2u : 0u);
-    P.s2_nsafe = nosum_env ? unanimous_cap_depth(c->h_tables.t, (uint32_t)o.min_input_base_quality & 0xFFu, 64u) : FGX_NEVER_CAP;
-  }
-  P.trim = o.trim; P.overlap = o.overlapping_consensus;
-  if (duplex) {   // single-strand caller of the duplex caller (duplex_caller.rs:474-489): min_reads 1, min consensus base quality 2
-    P.min_reads = 1; P.max_reads = -1; P.min_cons_bq = FGX_MIN_PHRED;
-    P.dmin_total = o.duplex_min_reads[0]; P.dmin_xy = o.duplex_min_reads[1]; P.dmin_yx = o.duplex_min_reads[2];
-    P.dmax_reads = o.duplex_max_reads_per_strand;
-    P.col_obs = d_obs.as<uint32_t>(); P.dends = d_ends.as<DuplexDesc>();
-  }
-  if (codec) {    // single-strand caller of the CODEC caller (codec_caller.rs:374-397): min_reads 1, no cap, min consensus base quality 0
-    P.min_reads = 1; P.max_reads = -1; P.min_cons_bq = 0; P.trim = 0; P.overlap = 0;
-    P.cends = d_ends.as<CodecDesc>(); P.cmin_reads = o.codec_min_reads_per_strand; P.cmax_reads = o.codec_max_reads_per_strand;
-    P.cmin_duplex_len = o.codec_min_duplex_length;
-  }
-  P.per_base_tags = o.produce_per_base_tags; P.track_rejects = o.track_rejects;
-  P.tag0 = (duplex || codec) ? 'M' : o.tag[0]; P.tag1 = (duplex || codec) ? 'I' : o.tag[1]; P.cell0 = o.cell_tag[0]; P.cell1 = o.cell_tag[1];
-  P.prefix_len = (uint32_t)c->prefix.size(); P.rg_len = (uint32_t)c->rg.size();
-  P.ends = d_ends.as<EndDesc>(); P.rec_sizes = d_sizes.as<uint64_t>();
-  P.col_code = d_code.as<uint8_t>(); P.col_qual = d_qual.as<uint8_t>(); P.col_depth = d_depth.as<uint16_t>(); P.col_err = d_err.as<uint16_t>();
-  if (meth_dev || meth_dup) {
-    const GenomeRef* gr = c->genome.get();
-    const uint32_t n_ref = (uint32_t)gr->off.size();
-    d_mcontigs.reserve((size_t)(n_ref + 1) * 16 + 64);
-    if (n_ref) {
-      hip_check(hipMemcpyAsync(d_mcontigs.p, gr->off.data(), (size_t)n_ref * 8, hipMemcpyHostToDevice, s), "H2D contig offsets");
-      hip_check(hipMemcpyAsync(d_mcontigs.as<uint64_t>() + n_ref, gr->len.data(), (size_t)n_ref * 8, hipMemcpyHostToDevice, s), "H2D contig lengths");
-    }
-    P.meth_mode = o.methylation_mode; P.n_ref = n_ref; P.genome = (const uint8_t*)gr->d_genome.p;
-    P.contig_off = d_mcontigs.as<uint64_t>(); P.contig_len = d_mcontigs.as<uint64_t>() + n_ref;
-    P.meth_flag = d_mflag.as<uint8_t>(); P.meth_u = d_mu.as<uint16_t>(); P.meth_t = d_mt.as<uint16_t>();
-  }
-  P.col_base = d_colbase.as<uint64_t>();
-  if (direct) {
-    P.dir_size = d_dir_size.as<uint32_t>(); P.dir_off = d_dir_off.as<uint64_t>(); P.out = d_out.as<uint8_t>(); P.out_cap = dir_cap;
-    P.out_off = d_offsets.as<uint64_t>(); P.slot_desc = d_slot_desc.as<SlotDesc>(); P.slot_err = d_slot_err.as<uint32_t>();
-    P.strings = d_strings.as<char>(); P.dir_flags = (uint32_t*)(misc + 36);
-  }
-  P.stats = d_statslots.as<unsigned long long>(); P.n_deferred = (uint32_t*)(misc + 29);
-  P.deferred = d_deferred.as<uint32_t>();
-  d_retry.reserve((size_t)n_grp * 4);
-  P.retry = d_retry.as<uint32_t>(); P.n_retry = (uint32_t*)(misc + 31);
-  P.group_list = nullptr;
-  // append lists for the columns that need call_full: room for 1/8 of the column bound (overflow → general path)
-  uint64_t full_total = col_cap / pool_div + (uint64_t)N_LISTS * pool_slack;
-  uint32_t full_cap = (uint32_t)std::min<uint64_t>(full_total / N_LISTS, 0x7FFFFFFFull);
-  d_full_items.reserve((size_t)full_cap * N_LISTS * sizeof(FullItem));
-  d_full_count.reserve((size_t)N_LISTS * 4);
-  hip_check(hipMemsetAsync(d_full_count.p, 0, (size_t)N_LISTS * 4, s), "memset");
-  P.full_items = d_full_items.as<FullItem>(); P.full_count = d_full_count.as<uint32_t>(); P.full_cap = full_cap;
-  uint32_t wave_bytes = duplex ? lds_wave_bytes_duplex : codec ? lds_wave_bytes_codec : lds_wave_bytes;
-  if (const char* e = fgx_knob("FGX_WAVE_BYTES")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 1024 && v <= 22016) wave_bytes = v & ~15u; }   // tuning knob
-  P.lds_wave_bytes = wave_bytes;
-  P.lds_tile_bytes = lds_tile_bytes_large;
-
-  // Wave-per-family launches over growing LDS slices: everything first, then only the groups whose records did not fit
-  // (long-tail families: 6 KB holds ~18 records of 150 bp, 12 KB ~36, 22 KB all 64 a wavefront can take).
-  {
-    const uint32_t stages[3] = {wave_bytes, 12288u, 22016u};
-    if (!lds_attr_set) {
-      hip_check(hipFuncSetAttribute((const void*)k_family_wave<0>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<0>: the device refused the dynamic LDS size");
-      hip_check(hipFuncSetAttribute((const void*)k_family_wave<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<1>: the device refused the dynamic LDS size");
-      hip_check(hipFuncSetAttribute((const void*)k_family_wave<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<2>: the device refused the dynamic LDS size");
-      hip_check(hipFuncSetAttribute((const void*)k_family_wave<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family_wave<1, 1>: the device refused the dynamic LDS size");
-      lds_attr_set = true;
-    }
-    d_retry2.reserve((size_t)n_grp * 4);
-    uint32_t* lists[2] = {d_retry.as<uint32_t>(), d_retry2.as<uint32_t>()};
-    // simplex families of more than 64 records: no wavefront-per-family kernel takes them — the first kernel that sees one puts it on
-    // k_family's list (round 3 walked them through k_simplex_wave2 and three k_family_wave<0> launches first: 2 ms per 1 M long-tail families)
-    uint32_t* d_cnt_big = (uint32_t*)(misc + 37);
-    uint32_t h_route_seen = 0, h_big_seen = 0;
-    bool split_counts_seen = false;
-    // (not with direct records: their merge pass walks ONE list of the families that left the split pipeline — the route list)
-    if (!duplex && !codec && !direct) { d_big.reserve((size_t)n_grp * 4); P.big = d_big.as<uint32_t>(); P.n_big = d_cnt_big; }
-    uint32_t* d_cnt = (uint32_t*)(misc + 31);
-    uint32_t n_cur = meth_dev ? 0u : n_grp;       // (methylation-aware mode: no wavefront-per-family kernel runs)
-    const uint32_t* cur_list = nullptr;
-    int out_list = 0;
-    // Simplex, no --trim: k_simplex_wave2 (two-accumulator column loop) takes the families of the common record shape over the same
-    // growing LDS slices; what is outside its shape is collected in `retry_old` and goes through the k_family_wave<0> launches below.
-    uint32_t n_v2 = n_grp;
-    const uint32_t* v2_list = nullptr;
-    last_split_chunks = 0;
-    if (use_split) {
-      // k_split_cols over growing LDS slices (4 / 2 / 1 / 1 wavefronts per workgroup); what it does not take is collected in
-      // `route` and starts the k_simplex_wave2 chain below
-        if (!s2_attr_set) {
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<0, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<0, 0, 0, 0>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<160, 80, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<160, 80, 0, 0>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<0, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<0, 0, 0, 1>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<160, 80, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<160, 80, 0, 1>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<0, 0, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<0, 0, 0, 2>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<160, 80, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<160, 80, 0, 2>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<0, 0, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<0, 0, 1, 0>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_split_cols<160, 80, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_split_cols<160, 80, 1, 0>: the device refused the dynamic LDS size");
-        s2_attr_set = true;
-      }
-      if (!d_s2img.p) {   // the tables of a caller never change: one image per FastPath
-        S2Image* img = new S2Image;
-        build_s2_image(*img, c->h_tables.t);
-        d_s2img.reserve(sizeof(S2Image));
-        hip_check(hipMemcpyAsync(d_s2img.p, img, sizeof(S2Image), hipMemcpyHostToDevice, s), "H2D s2 image");
-        FGX_SYNC(s);
-        delete img;
-      }
-      d_route.reserve((size_t)n_grp * 4);
-      uint32_t* d_cnt_route = (uint32_t*)(misc + 33);
-      P.s2_image = d_s2img.p; P.fam_desc = d_famdesc.as<uint4>();
-      P.split_rec = d_split_rec.as<SplitRec>(); P.split_fam = d_split_fam.as<SplitFam>();
-      d_split_out.reserve((size_t)n_grp * sizeof(SplitOut));
-      P.split_out = d_split_out.as<SplitOut>();
-      P.route = d_route.as<uint32_t>(); P.n_route = d_cnt_route;
-      // ---- the record kernel, chunk by chunk on a second stream: chunk i + 1 (waiting on memory most of its time) runs under the column
-      //      kernel of chunk i (bound by vector-instruction issue) ----------------------------------------------------------------------
-      d_split_rec.reserve((size_t)n_rec * sizeof(SplitRec) + 64);
-      d_split_fam.reserve((size_t)n_grp * sizeof(SplitFam) + 64);
-      P.split_rec = d_split_rec.as<SplitRec>(); P.split_fam = d_split_fam.as<SplitFam>();
-      split_streams();
-      FastParams PK;
-      split_parse_params(PK);
-      if (direct) { PK.dir_size = P.dir_size; PK.min_input_bq = o.min_input_base_quality; PK.per_base_tags = o.produce_per_base_tags; PK.rg_len = (uint32_t)c->rg.size(); }
-      uint32_t fpw, n_chunks, chunk_fam;
-      {
-        uint32_t chunk_fam_raw;
-        split_geometry(fpw, n_chunks, chunk_fam_raw, chunk_fam);
-        last_split_chunks = n_chunks;
-        dir_chunks_run = (n_grp + chunk_fam_raw - 1) / chunk_fam_raw;     // chunks that hold families (the rounding of chunk_fam can leave the last ones empty)
-      }
-      hip_check(hipEventRecord(ev_chunk[MAX_CHUNKS - 1], s), "event");      // (the second stream starts where this one is: buffers, memsets)
-      hip_check(hipStreamWaitEvent(s2, ev_chunk[MAX_CHUNKS - 1], 0), "wait");
-      size_t dir_scan_bytes = 0;
-      if (direct) {
-        const DirSizeIn in(d_dir_size.as<uint32_t>(), DirCast());
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, dir_scan_bytes, in, d_dir_off.as<uint64_t>(), (int)std::min<uint64_t>(chunk_fam, n_grp), s2);
-        d_scan_tmp2.reserve(dir_scan_bytes + 64);
-      }
-      auto launch_parse = [&](uint32_t ci) {
-        const uint32_t ga = ci * chunk_fam, gb = std::min<uint64_t>((uint64_t)ga + chunk_fam, n_grp);
-        if (ga >= gb) return;
-        const uint64_t waves = ((uint64_t)(gb - ga) + fpw - 1) / fpw;
-        do { last_launches++; hipLaunchKernelGGL(k_split_parse, dim3((uint32_t)((waves + 1) / 2)), dim3(128), 0, s2, PK, ga, gb, fpw, (uint64_t*)nullptr, 3u, (uint4*)nullptr); } while (0);
-        hip_check(hipGetLastError(), "k_split_parse launch");
-        if (direct) {   // the chunk's record offsets: exclusive scan of the predicted family sizes, carried on from the chunk before
-          const DirSizeIn in(d_dir_size.as<uint32_t>() + ga, DirCast());
-          hip_check(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp2.p, dir_scan_bytes, in, d_dir_off.as<uint64_t>() + ga, (int)(gb - ga), s2), "scan of the record sizes");
-          do { last_launches++; hipLaunchKernelGGL(k_dir_carry, dim3((gb - ga + 255) / 256), dim3(256), 0, s2, d_dir_off.as<uint64_t>() + ga, d_dir_size.as<uint32_t>() + ga, gb - ga,
-                             d_dir_base.as<uint64_t>() + ci); } while (0);
-          hip_check(hipGetLastError(), "k_dir_carry launch");
-        }
-        hip_check(hipEventRecord(ev_chunk[ci], s2), "event");
-      };
-      if (!early_parse) launch_parse(0);
-      // the tile strides of a sample of families decide which build of k_split_cols goes first: 64 families spread evenly over the first chunk (one strided
-      // copy; round 5 took the batch's FIRST 64 — the head of a coordinate-sorted file need not look like the rest)
-      SplitFam fam_sample[64];
-      // (at most one row per family of the first chunk: the rows past it are not parsed yet and hold what the previous batch left)
-      const uint32_t sample_span = (uint32_t)std::min<uint64_t>(chunk_fam, n_grp), sample_stride = std::max<uint32_t>(1u, sample_span / 64u);
-      const uint32_t n_sample = sample_span < 64u ? sample_span : 64u;
-      hip_check(hipMemcpy2DAsync(fam_sample, sizeof(SplitFam), d_split_fam.p, (size_t)sample_stride * sizeof(SplitFam), sizeof(SplitFam), n_sample, hipMemcpyDeviceToHost, s2), "D2H sample");
-      hip_check(hipEventRecord(ev_sample, s2), "event");
-      // (round 5) the record kernel is bound by HBM bandwidth (it reads the whole blob: 4.2 TB/s alone on the chip), and a column kernel
-      // beside it gets what is left — with every chunk's record kernel queued up front, the first column kernel took 6.9 ms instead of
-      // 1.7 and the two streams added up like one (gpurun_out timeline, profiles/r05_timeline_*.txt).  Paced: chunk k + 2 is parsed
-      // when the column kernel of chunk k has finished, i.e. under the column kernel of chunk k + 1.
-      static const int pace_env = [] { const char* e = fgx_knob("FGX_S2_PACE"); return e ? atoi(e) : 1; }();      // (measurement knob: 0 = all record kernels up front)
-      const bool paced = pace_env != 0 && n_chunks > 2;
-      for (uint32_t ci = 1; ci < (paced ? 2u : n_chunks); ci++) launch_parse(ci);
-      do { last_host_syncs++; hip_check(hipEventSynchronize(ev_sample), "sync"); } while (0);
-      // LDS slice of the first launch: the MEAN family's tile (rows of 160 + 80 bytes) + room for its k_call_full items, at least the
-      // 4352 bytes of a 16-record family — a deeper library starts at the slice its families need instead of failing the first launch
-      // as a whole (depth 12: every family took two launches, 32 ms per 1 M families)
-      static const uint32_t s2_bytes_env = [] { const char* e = fgx_knob("FGX_S2_BYTES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 2048 && v <= 32768 ? (v & ~15) : 0); }();
-      static const uint32_t s2_wpb_env = [] { const char* e = fgx_knob("FGX_S2_WPB"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 4 ? v : 0); }();
-      // (round 5: the packed pass sends every column it does not answer itself to k_call_full — also the one-base columns of too few
-      // observations, which run_cols's gates answer — and keeps an 8-byte descriptor per such column at the top of the slice: 56 bytes per
-      // column, ~14 columns per depth-8 family of `simulate` data; 5632 bytes x 4 wavefronts still leave a CU six workgroups)
-      bool s2_packed_on = !direct && P.s2_packed != 0 && P.s2_nsafe != FGX_NEVER_CAP && P.min_reads <= P.s2_nsafe && ((uint32_t)P.min_input_bq & 0xFFu) <= 128u;   // (what run_cols_packed asks of the caller's options)
-      // which of the two first-stage kernels the batch needs: by the sampled families (a family of the other kind still finds its way: the
-      // packed kernel without a partner hands it to the next launch, the partner kernel alone IS the classic kernel)
-      uint32_t n_pk = 0;
-      if (s2_packed_on) for (uint32_t i = 0; i < n_sample; i++) {
-        const SplitFam& F = fam_sample[i];
-        auto ok = [&](uint32_t m) { return m < 2u || (m >= P.s2_nsafe && m <= S2_PACKED_MAX_ROWS); };
-        n_pk += (ok(F.m_a) && ok(F.m_b) && ((F.len_a + 7u) >> 3) + ((F.len_b + 7u) >> 3) <= 64u) ? 1u : 0u;
-      }
-      static const int s2_partner_env = [] { const char* e = fgx_knob("FGX_S2_PARTNER"); return e ? atoi(e) : -1; }();   // (measurement knob: 1 = always both kernels, 0 = never)
-      if (s2_packed_on && n_sample && 100ull * n_pk < (unsigned long long)n_sample) s2_packed_on = false;               // under 1 % of its shape: the classic kernel alone
-      const bool s2_partner = s2_packed_on && (s2_partner_env >= 0 ? s2_partner_env != 0 : 100ull * n_pk < 99ull * n_sample);
-      last_split_build = s2_packed_on ? (s2_partner ? 2u : 1u) : 0u;
-      uint32_t s2_bytes0 = s2_packed_on ? 5632 : 4352;
-      {
-        const uint32_t mean_need = (uint32_t)(mean_recs + 0.999) * 240u + 16u + (s2_packed_on ? 1680u : 400u);
-        if (mean_need > s2_bytes0) s2_bytes0 = std::min<uint32_t>((mean_need + 15u) & ~15u, 17408u);
-      }
-      if (s2_bytes_env) s2_bytes0 = s2_bytes_env;
-      const uint32_t s2_wpb = s2_wpb_env ? s2_wpb_env : (s2_bytes0 <= 6528u ? 4u : s2_bytes0 <= 13056u ? 2u : 1u);
-      // rows of 160 + 80 bytes (reads up to 160 bases) have their own build: member rows at immediate offsets in the column loop
-      static const int s2_fixed_env = [] { const char* e = fgx_knob("FGX_S2_FIXED"); return e ? atoi(e) : -1; }();   // (measurement knob: 0 / 1)
-      uint32_t n160 = 0;
-      for (uint32_t i = 0; i < n_sample; i++) n160 += (fam_sample[i].qs == 160 && fam_sample[i].ss == 80) ? 1u : 0u;
-      const bool s2_fixed = s2_fixed_env >= 0 ? s2_fixed_env != 0 : 2 * n160 > n_sample;
-      struct S2Stage { uint32_t bytes, wpb; bool fixed; };
-      std::vector<S2Stage> st2;
-      // (reads of up to 160 bases: every slice size in the build with the strides as immediates, then ONE launch of the generic build for
-      // the families with other strides; round 3 ran the generic build from the second slice on — a long-tail batch spends most of its
-      // column time there)
-      if (s2_fixed) {
-        st2.push_back({s2_bytes0, s2_wpb, true});
-        st2.push_back({2 * s2_bytes0 > 8704u ? 2 * s2_bytes0 : 8704u, 2u, true});
-        st2.push_back({17408u, 1u, true});
-        st2.push_back({34816u, 1u, true});
-        st2.push_back({34816u, 1u, false});
-      } else {
-        st2.push_back({s2_bytes0, s2_wpb, false});
-        st2.push_back({2 * s2_bytes0 > 8704u ? 2 * s2_bytes0 : 8704u, 2u, false});
-        st2.push_back({17408u, 1u, false});
-        st2.push_back({34816u, 1u, false});
-      }
-      uint32_t n_s2 = n_grp;
-      const uint32_t* s2_list = nullptr;
-      int s2_out = 0;
-      for (size_t ci = 0; ci < st2.size() && n_s2; ci++) {
-        if (ci > 0 && st2[ci - 1].fixed == st2[ci].fixed && st2[ci].bytes <= st2[ci - 1].bytes) continue;
-        const bool last = ci + 1 == st2.size();
-        hip_check(hipMemsetAsync(d_cnt, 0, 4, s), "memset");
-        FastParams PS = P;
-        PS.group_list = s2_list; PS.lds_wave_bytes = st2[ci].bytes;
-        static const bool later_packed = [] { const char* e = fgx_knob("FGX_S2_LATER_PACKED"); return !(e && e[0] == '0'); }();   // (measurement knob: 0 = the classic build in the later stages, as in round 5)
-        PS.s2_partner = (s2_partner || (ci > 0 && later_packed && s2_packed_on)) ? 1u : 0u;
-        PS.retry = last ? nullptr : lists[s2_out]; PS.n_retry = d_cnt;
-        if (st2[ci].bytes > 65536u) continue;                 // (more than the attribute limit set above: the family goes down the chain)
-        const uint32_t wpb = std::min<uint32_t>(st2[ci].wpb, 65536u / st2[ci].bytes);   // wpb x slice within the 64 KiB requested for k_split_cols
-        const size_t lds = (size_t)wpb * st2[ci].bytes;
-        auto launch_cols = [&](uint32_t g_first, uint32_t count) {
-          PS.g0 = g_first;
-          const dim3 grid((count + wpb - 1) / wpb), block(64 * wpb);
-          if (direct) {
-            if (st2[ci].fixed) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<160, 80, 1, 0>), grid, block, lds, s, PS, count); } while (0);
-            else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<0, 0, 1, 0>), grid, block, lds, s, PS, count); } while (0);
-          } else if (s2_packed_on && (ci == 0 || later_packed)) {
-            // (round 5) the first stage as two launches over the same families: the packed pass for the families of its shape, run_cols for the rest;
-            // (round 6) the later stages — the families that need larger LDS slices: ends of 9 .. 31 rows — likewise, always as the pair (their lists are mixed)
-            const bool pair = s2_partner || ci > 0;
-            if (st2[ci].fixed) {
-              do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<160, 80, 0, 1>), grid, block, lds, s, PS, count); } while (0);
-              if (pair) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<160, 80, 0, 2>), grid, block, lds, s, PS, count); } while (0);
-            } else {
-              do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<0, 0, 0, 1>), grid, block, lds, s, PS, count); } while (0);
-              if (pair) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<0, 0, 0, 2>), grid, block, lds, s, PS, count); } while (0);
-            }
-          } else if (st2[ci].fixed) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<160, 80, 0, 0>), grid, block, lds, s, PS, count); } while (0);
-          else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_split_cols<0, 0, 0, 0>), grid, block, lds, s, PS, count); } while (0);
-        };
-        if (ci == 0) {   // the first stage takes the families in file order, chunk by chunk behind the record kernel
-          for (uint32_t k = 0; k < n_chunks; k++) {
-            const uint32_t ga = k * chunk_fam, gb = (uint32_t)std::min<uint64_t>((uint64_t)ga + chunk_fam, n_grp);
-            if (ga >= gb) break;
-            hip_check(hipStreamWaitEvent(s, ev_chunk[k], 0), "wait");
-            launch_cols(ga, gb - ga);
-            // the chunk's EndDescs / record sizes / counters (a thread per family: waits on memory, few instructions) on the second
-            // stream, under the next chunk's column kernel
-            hip_check(hipEventRecord(ev_cols[k], s), "event");
-            hip_check(hipStreamWaitEvent(s2, ev_cols[k], 0), "wait");
-            FastParams PF = P;
-            PF.group_list = nullptr; PF.g0 = ga;
-            do { last_launches++; hipLaunchKernelGGL(k_split_finish, dim3((gb - ga + 255) / 256), dim3(256), 0, s2, PF, gb - ga); } while (0);
-            if (paced && k + 2 < n_chunks) launch_parse(k + 2);
-          }
-        } else {
-          launch_cols(0u, n_s2);
-          FastParams PF = P;                       // the families this (larger-slice) launch finished: the list it was given
-          PF.group_list = s2_list; PF.g0 = 0;
-          do { last_launches++; hipLaunchKernelGGL(k_split_finish, dim3((n_s2 + 255) / 256), dim3(256), 0, s, PF, n_s2); } while (0);
-        }
-        hip_check(hipGetLastError(), "k_split_cols launch");
-        // (round 6: the route / big counters come along — after the LAST stage they are final, and two host synchronisations of their own go away;
-        // the three are words 31, 33 and 37 of `misc`: ONE copy of its words 31 .. 37)
-        unsigned long long h_cnt7[7] = {0, 0, 0, 0, 0, 0, 0};
-        static_assert(sizeof(h_cnt7) == 56, "misc words 31 .. 37");
-        hip_check(hipMemcpyAsync(h_cnt7, misc + 31, sizeof(h_cnt7), hipMemcpyDeviceToHost, s), "D2H");
-        split_counts_seen = true;
-        FGX_SYNC(s);
-        const uint32_t n_next = (uint32_t)h_cnt7[0];
-        h_route_seen = (uint32_t)h_cnt7[2]; h_big_seen = (uint32_t)h_cnt7[6];
-        if (ci == 0) last_first_stage_retries = PS.retry ? n_next : 0u;
-        s2_list = lists[s2_out]; n_s2 = PS.retry ? n_next : 0; s2_out ^= 1;
-      }
-      hip_check(hipEventRecord(ev_fin, s2), "event");          // the per-chunk k_split_finish launches
-      hip_check(hipStreamWaitEvent(s, ev_fin, 0), "wait");
-      uint32_t n_route = h_route_seen;
-      if (!split_counts_seen) {
-        hip_check(hipMemcpyAsync(&n_route, d_cnt_route, 4, hipMemcpyDeviceToHost, s), "D2H");
-        FGX_SYNC(s);
-      }
-      n_v2 = n_route; v2_list = d_route.as<uint32_t>();
-      last_routed = n_route;
-      static const bool s2_verbose = [] { const char* e = fgx_knob("FGX_S2_VERBOSE"); return e && e[0] == '1'; }();
-      if (s2_verbose) fprintf(stderr, "[fgx] split pipeline: %u families, %u routed to k_simplex_wave2\n", n_grp, n_route);
-    }
-    if (simplex_v2) {
-      // Launch chain: k_simplex_seg<4> / <2> (4 / 2 families per wavefront, while the mean family fits a quarter / half of the
-      // wave's LDS) → k_simplex_wave2 over the growing slices.  A family that does not fit a launch moves to the next one.
-        if (!v2_attr_set) {
-        hip_check(hipFuncSetAttribute((const void*)k_simplex_wave2, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 22016), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_simplex_wave2: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_simplex_seg<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 32768), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_simplex_seg<2>: the device refused the dynamic LDS size");
-        hip_check(hipFuncSetAttribute((const void*)k_simplex_seg<4>, hipFuncAttributeMaxDynamicSharedMemorySize, WAVES_PER_BLOCK * 32768), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_simplex_seg<4>: the device refused the dynamic LDS size");
-        v2_attr_set = true;
-      }
-      if (!d_w2img.p) {   // the tables of a caller never change: one image per FastPath
-        W2Lds img;
-        build_w2_image(img, c->h_tables.t);
-        d_w2img.reserve(sizeof(W2Lds));
-        hip_check(hipMemcpyAsync(d_w2img.p, &img, sizeof(W2Lds), hipMemcpyHostToDevice, s), "H2D w2 image");
-        FGX_SYNC(s);             // (`img` is on this stack frame)
-      }
-      P.w2_image = d_w2img.p;
-      P.fam_desc = d_famdesc.as<uint4>();
-      struct Stage { int fam_per_wave; uint32_t bytes; uint32_t wpb; };
-      std::vector<Stage> chain;
-      static const uint32_t seg_wpb = [] { const char* e = fgx_knob("FGX_SEG_WPB"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= WAVES_PER_BLOCK ? v : WAVES_PER_BLOCK); }();   // (measurement knob)
-      if (use_seg && mean_span + (16 * 8 + 64) <= seg_bytes / 4) chain.push_back({4, seg_bytes, seg_wpb});
-      // (two families per wavefront measured slower than one at depth 8 — 14.9 vs 10.7 ms per 1 M families: the column phase costs
-      // the same per family and a CU holds 12 instead of 20 wavefronts; kept behind FGX_SEG2=1 for experiments)
-      static const bool use_seg2 = [] { const char* e = fgx_knob("FGX_SEG2"); return e && e[0] == '1'; }();
-      if (use_seg && use_seg2 && mean_span + (32 * 8 + 64) <= seg_bytes / 2) chain.push_back({2, seg_bytes, (uint32_t)WAVES_PER_BLOCK});
-      // (Two workgroup-cooperative variants were built, verified byte-identical and measured slower — the record phases of four
-      // families on ONE wavefront while the other three wait at a barrier, 11.9 ms, and the same as a producer / consumer pipeline
-      // in persistent workgroups, 19.3 ms, against 10.2 ms per 1 M depth-8 families here: they execute 20 % fewer vector and 43 %
-      // fewer scalar instructions, but a lone wavefront retires an instruction every ~30 cycles, and the CU is fed by the number of
-      // independent wavefronts, not by lane utilisation.  profiles/r02c_pmc_1M_blk.json, r02d_pmc_1M_pipe.json; HISTORY.md §4.)
-      // wavefronts per workgroup of k_simplex_wave2's first launch: the LDS of a workgroup is freed when its SLOWEST wavefront is
-      // done, so small workgroups keep more wavefronts running (FGX_W2_WPB: measurement knob)
-      static const uint32_t w2_wpb = [] { const char* e = fgx_knob("FGX_W2_WPB"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= WAVES_PER_BLOCK ? v : FGX_W2_WPB_DEFAULT); }();
-      for (int st = 0; st < 3; st++) if (st == 0 || stages[st] > stages[st - 1]) chain.push_back({1, stages[st], st == 0 ? w2_wpb : st == 1 ? 2u : 1u});
-      d_retry_old.reserve((size_t)n_grp * 4);
-      uint32_t* d_cnt_old = (uint32_t*)(misc + 32);
-      int v2_out = 0;
-      bool v2_ran = false;
-      for (size_t ci = 0; ci < chain.size() && n_v2; ci++) {
-        v2_ran = true;
-        const Stage& S = chain[ci];
-        const bool last = ci + 1 == chain.size();
-        hip_check(hipMemsetAsync(d_cnt, 0, 4, s), "memset");
-        FastParams PS = P;
-        PS.group_list = v2_list; PS.lds_wave_bytes = S.bytes;
-        PS.retry = last ? nullptr : lists[v2_out]; PS.n_retry = d_cnt;
-        PS.retry_old = d_retry_old.as<uint32_t>(); PS.n_retry_old = d_cnt_old;
-        const uint32_t fpb = S.wpb * (uint32_t)S.fam_per_wave;      // families per workgroup
-        const dim3 grid((n_v2 + fpb - 1) / fpb), block(64 * S.wpb);
-        const size_t lds = (size_t)S.wpb * S.bytes;
-        if (S.fam_per_wave == 4) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_simplex_seg<4>), grid, block, lds, s, PS, n_v2); } while (0);
-        else if (S.fam_per_wave == 2) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_simplex_seg<2>), grid, block, lds, s, PS, n_v2); } while (0);
-        else do { last_launches++; hipLaunchKernelGGL(k_simplex_wave2, grid, block, lds, s, PS, n_v2); } while (0);
-        hip_check(hipGetLastError(), "k_simplex launch");
-        uint32_t n_next = 0;
-        hip_check(hipMemcpyAsync(&n_next, d_cnt, 4, hipMemcpyDeviceToHost, s), "D2H");
-        FGX_SYNC(s);
-        v2_list = lists[v2_out]; n_v2 = PS.retry ? n_next : 0; v2_out ^= 1;
-      }
-      uint32_t n_old = 0;
-      if (v2_ran) {   // (no kernel of the chain has run — the split pipeline kept every family —: nothing to read, no synchronisation)
-        hip_check(hipMemcpyAsync(&n_old, d_cnt_old, 4, hipMemcpyDeviceToHost, s), "D2H");
-        FGX_SYNC(s);
-      }
-      n_cur = n_old; cur_list = d_retry_old.as<uint32_t>();
-      out_list = 0;
-    }
-    for (int st = 0; st < 3 && n_cur; st++) {
-      if (st > 0 && stages[st] <= stages[st - 1]) continue;
-      const bool last = st == 2;
-      hip_check(hipMemsetAsync(d_cnt, 0, 4, s), "memset");
-      FastParams PS = P;
-      PS.group_list = cur_list; PS.lds_wave_bytes = stages[st];
-      PS.retry = (last && (duplex || codec)) ? nullptr : lists[out_list]; PS.n_retry = d_cnt;
-      // fewer wavefronts per workgroup as the slices grow: the LDS a workgroup asks for is what limits the wavefronts a CU holds
-      // (4 x 22 KB = one workgroup = 4 waves per CU; 1 x 22 KB = six workgroups = 6 waves)
-      static const uint32_t fw_wpb = [] { const char* e = fgx_knob("FGX_FW_WPB"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= WAVES_PER_BLOCK ? v : WAVES_PER_BLOCK); }();   // (measurement knob)
-      const uint32_t wpb = st == 0 ? fw_wpb : st == 1 ? 2u : 1u;
-      const dim3 grid((n_cur + wpb - 1) / wpb), block(64 * wpb);
-      const size_t lds = (size_t)wpb * stages[st];
-      if (codec) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<2>), grid, block, lds, s, PS, n_cur); } while (0);
-      else if (meth_dup) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<1, 1>), grid, block, lds, s, PS, n_cur); } while (0);
-      else if (duplex) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<1>), grid, block, lds, s, PS, n_cur); } while (0);
-      else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_family_wave<0>), grid, block, lds, s, PS, n_cur); } while (0);
-      hip_check(hipGetLastError(), "k_family_wave launch");
-      uint32_t n_next = 0;
-      hip_check(hipMemcpyAsync(&n_next, d_cnt, 4, hipMemcpyDeviceToHost, s), "D2H");
-      FGX_SYNC(s);
-      cur_list = lists[out_list]; n_cur = PS.retry ? n_next : 0; out_list ^= 1;
-    }
-    if (meth_dup) last_meth_device = n_grp;
-    uint32_t n_big = 0;
-    if (!duplex && !codec) {
-      if (split_counts_seen && last_routed == 0) n_big = h_big_seen;   // (no kernel after the split stages has run: what their last synchronisation read is final)
-      else {
-        hip_check(hipMemcpyAsync(&n_big, d_cnt_big, 4, hipMemcpyDeviceToHost, s), "D2H");
-        FGX_SYNC(s);
-      }
-    }
-    if (meth_dev) {
-      d_big.reserve((size_t)n_grp * 4);
-      do { last_launches++; hipLaunchKernelGGL(k_iota, dim3((n_grp + 255) / 256), dim3(256), 0, s, d_big.as<uint32_t>(), n_grp); } while (0);
-      n_big = n_grp;
-    }
-    last_big_families = n_big;
-    last_deep_families = 0;
-    // ---- deep families: k_deep_parse + k_deep_cols (simplex_deep.inc) take the big list; what is outside their shape goes on to k_family ----
-    const bool use_deep = [] { const char* e = getenv("FGX_DEEP"); return !(e && e[0] == '0'); }();   // (read per batch)
-    const uint32_t* big_list = d_big.as<uint32_t>();
-    if (n_big && (use_deep || meth_dev) && !o.trim) {
-      if (!d_s2img.p) {   // (the column kernel's LDS tables: the split pipeline's image)
-        S2Image* img = new S2Image;
-        build_s2_image(*img, c->h_tables.t);
-        d_s2img.reserve(sizeof(S2Image));
-        hip_check(hipMemcpyAsync(d_s2img.p, img, sizeof(S2Image), hipMemcpyHostToDevice, s), "H2D s2 image");
-        FGX_SYNC(s);
-        delete img;
-      }
-      P.s2_image = d_s2img.p;
-      uint32_t* d_cnt_deep = (uint32_t*)(misc + 38);
-      // one pass of the streaming kernels over a family list; returns how many families it handed on (to `out_list`)
-      // `size_class`: 0 = the wavefront-sized build of the record kernel (families of up to 64 records), 1 = two wavefronts (up to 128), 2 = four (up to DEEP_MAX)
-      auto deep_pass = [&](const uint32_t* list, uint32_t n_list, int size_class, uint32_t* out_list) -> uint32_t {
-        d_deep_sizes.reserve((size_t)n_list * 8 + 64); d_deep_row0.reserve((size_t)n_list * 8 + 64);
-        do { last_launches++; hipLaunchKernelGGL(k_deep_sizes, dim3((n_list + 255) / 256), dim3(256), 0, s, list, n_list, d_grp_first, d_deep_sizes.as<uint64_t>()); } while (0);
-        size_t tb = 0;
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_deep_sizes.as<uint64_t>(), d_deep_row0.as<uint64_t>(), (int)n_list, s);
-        d_scan_tmp.reserve(tb);
-        hip_check(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tb, d_deep_sizes.as<uint64_t>(), d_deep_row0.as<uint64_t>(), (int)n_list, s), "scan of the deep families' records");
-        uint64_t lastr[2] = {0, 0};
-        hip_check(hipMemcpyAsync(&lastr[0], d_deep_row0.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
-        hip_check(hipMemcpyAsync(&lastr[1], d_deep_sizes.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
-        FGX_SYNC(s);
-        const uint64_t n_rows = lastr[0] + lastr[1];
-        if (n_rows > (uint64_t)n_rec) throw std::runtime_error("device pipeline: " + std::to_string(n_rows) + " rows for the streaming kernels, more than the batch has records");
-        d_deep_rows.reserve((size_t)n_rows * sizeof(DeepRow) + 64); d_deep_fams.reserve((size_t)n_list * sizeof(DeepFam) + 64);
-        hip_check(hipMemsetAsync(d_cnt_deep, 0, 4, s), "memset");
-        DeepParams DP;
-        DP.list = list; DP.n_list = n_list; DP.row0 = d_deep_row0.as<uint64_t>();
-        DP.rows = d_deep_rows.as<DeepRow>(); DP.fams = d_deep_fams.as<DeepFam>(); DP.out_list = out_list; DP.n_out = d_cnt_deep;
-        FastParams PD = P;
-        PD.group_list = nullptr;
-        if (size_class == 0) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deep_parse<64, 64>), dim3(n_list), dim3(64), 0, s, PD, DP); } while (0);
-        else if (size_class == 1) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP); } while (0);
-        else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP); } while (0);
-        hip_check(hipGetLastError(), "k_deep_parse launch");
-        if (meth_dev) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deep_cols<1>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP); } while (0);
-        else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deep_cols<0>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP); } while (0);
-        hip_check(hipGetLastError(), "k_deep_cols launch");
-        uint32_t n_left = 0;
-        hip_check(hipMemcpyAsync(&n_left, d_cnt_deep, 4, hipMemcpyDeviceToHost, s), "D2H");
-        FGX_SYNC(s);
-        return n_left;
-      };
-      d_deep_out.reserve((size_t)n_big * 4 + 64);
-      if (meth_dev) {
-        // every family: the wavefront-sized build of the record kernel first, the workgroup-sized one for the families above 64 records;
-        // what neither takes is on the deferred list (the general path knows the mode)
-        const uint32_t n_large = deep_pass(d_big.as<uint32_t>(), n_big, 0, d_deep_out.as<uint32_t>());
-        if (n_large) {
-          d_deep_out2.reserve((size_t)n_large * 4 + 64);
-          (void)deep_pass(d_deep_out.as<uint32_t>(), n_large, 2, d_deep_out2.as<uint32_t>());
-        }
-        last_deep_families = n_big;
-        last_meth_device = n_grp; n_big = 0;
-      } else {
-        // (round 6) two wavefronts per family first: a family of 65 .. 128 records — every deep family of a 2 .. 50-pair long tail — kept a quarter to a
-        // half of the 256 threads of the large build busy in the record kernel; what has more records (or is not the kernels' shape) goes on to the large build
-        const uint32_t n_mid = deep_pass(d_big.as<uint32_t>(), n_big, 1, d_deep_out.as<uint32_t>());
-        uint32_t n_left = 0;
-        big_list = d_deep_out.as<uint32_t>();
-        if (n_mid) {
-          d_deep_out2.reserve((size_t)n_mid * 4 + 64);
-          n_left = deep_pass(d_deep_out.as<uint32_t>(), n_mid, 2, d_deep_out2.as<uint32_t>());
-          big_list = d_deep_out2.as<uint32_t>();
-        }
-        last_deep_families = n_big - n_left;
-        n_big = n_left;
-      }
-    }
-    // more than 64 records (the list the first kernels filled), or more bytes than the largest slice (what the chain left): one workgroup per family
-    for (int pass = 0; pass < 2 && !duplex && !codec; pass++) {
-      const uint32_t cnt = pass == 0 ? n_cur : n_big;
-      if (!cnt) continue;
-      FastParams P2 = P;
-      P2.group_list = pass == 0 ? cur_list : big_list; P2.retry = nullptr; P2.n_retry = nullptr;
-      if (const char* e = fgx_knob("FGX_LDS_TILE_LARGE")) { uint32_t v = (uint32_t)atoi(e); if (v >= 16384 && v <= 163840) lds_tile_bytes_large = v & ~15u; P2.lds_tile_bytes = lds_tile_bytes_large; }   // tuning knob
-      hip_check(hipFuncSetAttribute((const void*)k_family, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile_bytes_large), "hipFuncSetAttribute(MaxDynamicSharedMemorySize) for k_family: the device refused the dynamic LDS size");
-      do { last_launches++; hipLaunchKernelGGL(k_family, dim3(cnt), dim3(NT), lds_tile_bytes_large, s, P2); } while (0);
-      hip_check(hipGetLastError(), "k_family (large) launch");
-    }
-  }
-  uint64_t n_full = 0;
-  {   // dense call_full pass over the compacted lists
-    std::vector<uint32_t> counts(N_LISTS);
-    hip_check(hipMemcpyAsync(counts.data(), d_full_count.p, (size_t)N_LISTS * 4, hipMemcpyDeviceToHost, s), "D2H");
-    FGX_SYNC(s);
-    uint32_t mx = 0, mn = 0xFFFFFFFFu;
-    for (uint32_t v : counts) { uint32_t vv = v < full_cap ? v : full_cap; mx = vv > mx ? vv : mx; mn = v < mn ? v : mn; n_full += vv; }
-    if (mn >= full_cap && pool_div > 1) {
-      // every list is full: some family found no room (and was deferred).  Twice the room, if the device has it, and the batch again.
-      size_t free_b = 0, total_b = 0;
-      (void)hipMemGetInfo(&free_b, &total_b);
-      const uint64_t want = (col_cap / (pool_div / 2) + (uint64_t)N_LISTS * pool_slack) * sizeof(FullItem);
-      if (want < (uint64_t)free_b + (uint64_t)d_full_items.cap) {
-        pool_div /= 2;
-        static const bool verbose = [] { const char* e = fgx_knob("FGX_S2_VERBOSE"); return e && e[0] == '1'; }();
-        if (verbose) fprintf(stderr, "[fgx] call_full pool exhausted: the batch again with 1/%u of the column bound\n", pool_div);
-        return RUN_AGAIN_LARGER_POOL;
-      }
-    }
-    if (mx) {
-      FullParams F;
-      memset(&F, 0, sizeof(F));
-      F.items = d_full_items.as<FullItem>(); F.count = d_full_count.as<uint32_t>(); F.cap = full_cap;
-      F.T = P.T; F.TU = P.TU; F.min_reads = P.min_reads; F.min_cons_bq = P.min_cons_bq;
-      F.col_code = P.col_code; F.col_qual = P.col_qual; F.col_err = P.col_err;
-      F.col_depth = P.col_depth; F.min_input_bq = P.min_input_bq;
-      F.out = P.out; F.slot_desc = P.slot_desc; F.slot_err = P.slot_err; F.rg_len = P.rg_len; F.per_base_tags = P.per_base_tags;
-      if (duplex) { F.rx_base = (char*)P.dends + offsetof(DuplexDesc, rx); F.rx_stride = sizeof(DuplexDesc); }
-      else if (codec) { F.rx_base = (char*)P.cends + offsetof(CodecDesc, rx); F.rx_stride = sizeof(CodecDesc); }
-      else { F.rx_base = (char*)P.ends + offsetof(EndDesc, rx); F.rx_stride = sizeof(EndDesc); }
-      do { last_launches++; hipLaunchKernelGGL(k_call_full, dim3((mx + 255) / 256, N_LISTS), dim3(256), 0, s, F); } while (0);
-      hip_check(hipGetLastError(), "k_call_full launch");
-    }
-  }
-  if (meth_dev) {   // the methylation tags' share of the record sizes: the consensus bases are final now
-    do { last_launches++; hipLaunchKernelGGL(k_meth_sizes, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<MethSlot>()); } while (0);
-    hip_check(hipGetLastError(), "k_meth_sizes launch");
-  }
-  if (meth_dup) {
-    do { last_launches++; hipLaunchKernelGGL(k_duplex_meth_sizes, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<DuplexMethSlot>()); } while (0);
-    hip_check(hipGetLastError(), "k_duplex_meth_sizes launch");
-  }
-  // ---- direct records: cE of the records whose columns had errors; did every prediction hold; is there anything to merge? ----------
-  bool dir_pure = false;
-  uint32_t dir_routed = 0;
-  uint64_t dir_total = 0;
-  if (direct) {
-    do { last_launches++; hipLaunchKernelGGL(k_fix_ce, dim3((n_slots + 255) / 256), dim3(256), 0, s, d_slot_desc.as<SlotDesc>(), d_slot_err.as<uint32_t>(), n_slots, d_out.as<uint8_t>(), P.rg_len); } while (0);
-    hip_check(hipGetLastError(), "k_fix_ce launch");
-    unsigned long long h_flags = 0, h_def = 0, h_route = 0;
-    hip_check(hipMemcpyAsync(&h_flags, misc + 36, 8, hipMemcpyDeviceToHost, s), "D2H");
-    hip_check(hipMemcpyAsync(&h_def, misc + 29, 8, hipMemcpyDeviceToHost, s), "D2H");
-    hip_check(hipMemcpyAsync(&h_route, misc + 33, 8, hipMemcpyDeviceToHost, s), "D2H");
-    hip_check(hipMemcpyAsync(&dir_total, d_dir_base.as<uint64_t>() + dir_chunks_run, 8, hipMemcpyDeviceToHost, s), "D2H");
-    FGX_SYNC(s);
-    static const bool dir_verbose = [] { const char* e = fgx_knob("FGX_S2_VERBOSE"); return e && e[0] == '1'; }();
-    if ((uint32_t)h_flags != 0) {          // a family's records are not what k_split_parse predicted: nothing of the batch can be trusted to be in place
-      fprintf(stderr, "[fgx] direct records: %u families differ in size from the prediction; this caller goes back to the column scratch (please report)\n", (uint32_t)h_flags);
-      direct_off = true;
-      return RUN_AGAIN_LARGER_POOL;
-    }
-    if ((uint32_t)(h_flags >> 32) != 0) {  // more record bytes than the first estimate of the room: the exact amount is known now
-      dir_cap_min = dir_total + dir_total / 16 + 4096;
-      if (dir_verbose) fprintf(stderr, "[fgx] direct records: the batch needs %llu bytes of output, %llu were at hand: again\n", (unsigned long long)dir_total, (unsigned long long)dir_cap);
-      return RUN_AGAIN_LARGER_POOL;
-    }
-    dir_routed = (uint32_t)h_route;
-    dir_pure = dir_routed == 0 && (uint32_t)h_def == 0;
-    last_direct = dir_pure ? 1 : 2;
-    if (dir_verbose) fprintf(stderr, "[fgx] direct records: %llu bytes in place, %u families left the split pipeline, %u deferred\n", (unsigned long long)dir_total, dir_routed, (uint32_t)h_def);
-  }
-  hip_check(hipEventRecord(ev[1], s), "event");
-
-  uint64_t out_len = dir_total;
-  uint8_t* out_ptr = d_out.as<uint8_t>();
-  if (!dir_pure) {
-    size_t tmp_bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_sizes.as<uint64_t>(), d_offsets.as<uint64_t>(), (int)n_slots + 1, s);
-    d_scan_tmp.reserve(tmp_bytes);
-    hip_check(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes, d_sizes.as<uint64_t>(), d_offsets.as<uint64_t>(), (int)n_slots + 1, s), "scan");
-
-    // total output size = last offset + last size
-    // total output size = the scan's element behind the last slot (d_sizes[n_slots] is 0)
-    uint64_t out_total = 0;
-    hip_check(hipMemcpyAsync(&out_total, d_offsets.as<uint64_t>() + n_slots, 8, hipMemcpyDeviceToHost, s), "D2H");
-    FGX_SYNC(s);
-    out_len = out_total;
-    if (out_len > (1ull << 40)) throw std::runtime_error("device pipeline: the scan of the record sizes gives " + std::to_string(out_len) + " bytes of output (a record size is corrupt)");
-    if (direct) { d_out2.reserve(out_len + 16); out_ptr = d_out2.as<uint8_t>(); }   // the merged stream: d_out holds the directly written records
-    else { d_out.reserve(out_len + 16); out_ptr = d_out.as<uint8_t>(); }
-  }
-
-  EmitParams E;
-  memset(&E, 0, sizeof(E));
-  E.blob = d_blob; E.rec_off = d_rec_off; E.ends = d_ends.as<EndDesc>(); E.out_off = d_offsets.as<uint64_t>(); E.out = out_ptr;
-  E.out_base = 0; E.slot0 = 0; E.slot_end = n_slots;
-  E.col_code = P.col_code; E.col_qual = P.col_qual; E.col_depth = P.col_depth; E.col_err = P.col_err;
-  E.prefix = d_strings.as<char>(); E.prefix_len = P.prefix_len; E.rg = d_strings.as<char>() + P.prefix_len; E.rg_len = P.rg_len;
-  E.per_base_tags = P.per_base_tags; E.tag0 = P.tag0; E.tag1 = P.tag1; E.cell0 = P.cell0; E.cell1 = P.cell1;
-  hip_check(hipEventRecord(ev[2], s), "event");
-  // (round 6) duplex / CODEC: the per-field record writer (k_emit_duplex / k_emit_codec: any length, any tag size) used to run over EVERY slot behind the fast
-  // writer and find nothing to do (0.97 / 0.33 ms per step of wavefronts that load a descriptor and leave); a counting kernel (a thread per slot) now says
-  // how many records the fast writer refuses, and the per-field kernel is launched — after the batch's last synchronisation — only when there are any
-  DuplexEmitParams DE_late;
-  CodecEmitParams CE_late;
-  int late_emit = 0;
-  if (codec) {
-    CodecEmitParams CE;
-    memset(&CE, 0, sizeof(CE));
-    CE.blob = d_blob; CE.rec_off = d_rec_off; CE.ends = d_ends.as<CodecDesc>(); CE.out_off = d_offsets.as<uint64_t>(); CE.out = d_out.as<uint8_t>();
-    CE.slot0 = 0; CE.slot_end = n_slots;
-    CE.col_code = P.col_code; CE.col_qual = P.col_qual; CE.col_depth = P.col_depth; CE.col_err = P.col_err;
-    CE.prefix = E.prefix; CE.prefix_len = E.prefix_len; CE.rg = E.rg; CE.rg_len = E.rg_len;
-    CE.per_base_tags = P.per_base_tags; CE.cell0 = P.cell0; CE.cell1 = P.cell1;
-    CE.has_outer = o.codec_has_outer_bases_qual; CE.outer_qual = o.codec_outer_bases_qual; CE.outer_len = o.codec_outer_bases_length;
-    CE.has_ss = o.codec_has_single_strand_qual; CE.ss_qual = o.codec_single_strand_qual;
-    CE.stats = d_statslots.as<unsigned long long>();
-    CE.n_slow = (uint32_t*)(misc + 44);
-    CE_late = CE; late_emit = 2;
-    do { last_launches++; hipLaunchKernelGGL(k_count_slow_codec, dim3((n_slots + 255) / 256), dim3(256), 0, s, CE.ends, 0u, n_slots, CE.prefix_len, CE.rg_len, CE.n_slow); } while (0);
-    do { last_launches++; hipLaunchKernelGGL(k_emit_codec_fast, dim3((n_slots + 3) / 4), dim3(256), 0, s, CE); } while (0);
-  } else if (duplex) {
-    DuplexEmitParams DE;
-    memset(&DE, 0, sizeof(DE));
-    DE.blob = d_blob; DE.rec_off = d_rec_off; DE.ends = d_ends.as<DuplexDesc>(); DE.out_off = d_offsets.as<uint64_t>(); DE.out = d_out.as<uint8_t>();
-    DE.slot0 = 0; DE.slot_end = n_slots;
-    DE.col_code = P.col_code; DE.col_qual = P.col_qual; DE.col_err = P.col_err; DE.col_obs = P.col_obs;
-    DE.prefix = E.prefix; DE.prefix_len = E.prefix_len; DE.rg = E.rg; DE.rg_len = E.rg_len;
-    DE.per_base_tags = P.per_base_tags; DE.cell0 = P.cell0; DE.cell1 = P.cell1;
-    DE.n_slow = (uint32_t*)(misc + 44);
-    DE.meth_flag = P.meth_flag;
-    DE_late = DE; late_emit = 1;
-    do { last_launches++; hipLaunchKernelGGL(k_count_slow_duplex, dim3((n_slots + 255) / 256), dim3(256), 0, s, DE.ends, 0u, n_slots, DE.prefix_len, DE.rg_len, DE.n_slow); } while (0);
-    if (meth_dup) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex_fast<1>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE); } while (0);
-    else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex_fast<0>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE); } while (0);
-  } else if (direct) {
-    if (!dir_pure) {
-      // the merge: the families that left the split pipeline are written by k_emit from their descriptors, the directly written ones move
-      // to their place in the final stream
-      if (dir_routed) {
-        E.fam_list = d_route.as<uint32_t>(); E.n_fam = dir_routed;
-        do { last_launches++; hipLaunchKernelGGL(k_emit, dim3((dir_routed + 3) / 4), dim3(256), 0, s, E); } while (0);
-      }
-      do { last_launches++; hipLaunchKernelGGL(k_dir_copy, dim3((n_grp + 3) / 4), dim3(256), 0, s, d_split_out.as<SplitOut>(), d_dir_off.as<uint64_t>(), d_offsets.as<uint64_t>(),
-                         d_sizes.as<uint64_t>(), d_out.as<uint8_t>(), out_ptr, n_grp); } while (0);
-    }
-  } else do { last_launches++; hipLaunchKernelGGL(k_emit, dim3((n_grp + 3) / 4), dim3(256), 0, s, E); } while (0);   // one wavefront per family (slots 3g .. 3g + 2)
-  hip_check(hipGetLastError(), "k_emit launch");
-  if (meth_dev) {
-    do { last_launches++; hipLaunchKernelGGL(k_meth_tail, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<MethSlot>(), d_offsets.as<uint64_t>(), out_ptr); } while (0);
-    hip_check(hipGetLastError(), "k_meth_tail launch");
-  }
-  if (meth_dup) {
-    do { last_launches++; hipLaunchKernelGGL(k_duplex_meth_tail, dim3((n_slots + 3) / 4), dim3(256), 0, s, P, n_slots, d_mslot.as<DuplexMethSlot>(), d_offsets.as<uint64_t>(), out_ptr); } while (0);
-    hip_check(hipGetLastError(), "k_duplex_meth_tail launch");
-  }
-  hip_check(hipEventRecord(ev[3], s), "event");
-  hip_check(hipEventRecord(c->ev1, s), "event");
-  do { last_launches++; hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, s, d_statslots.as<unsigned long long>(), misc); } while (0);
-  unsigned long long h_misc[46];
-  hip_check(hipMemcpyAsync(h_misc, misc, sizeof(h_misc), hipMemcpyDeviceToHost, s), "D2H");
-  FGX_SYNC(s);
-  if (late_emit && (uint32_t)h_misc[44] != 0) {     // records the fast writer left: the per-field kernel, then the counters again (the CODEC writer counts bases)
-    if (late_emit == 2) do { last_launches++; hipLaunchKernelGGL(k_emit_codec, dim3((n_slots + 3) / 4), dim3(256), 0, s, CE_late); } while (0);
-    else if (meth_dup) do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex<1>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE_late); } while (0);
-    else do { last_launches++; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_emit_duplex<0>), dim3((n_slots + 3) / 4), dim3(256), 0, s, DE_late); } while (0);
-    hip_check(hipGetLastError(), "per-field record writer launch");
-    do { last_launches++; hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(64), 0, s, d_statslots.as<unsigned long long>(), misc); } while (0);
-    hip_check(hipMemcpyAsync(h_misc, misc, sizeof(h_misc), hipMemcpyDeviceToHost, s), "D2H");
-    FGX_SYNC(s);
-  }
-  float ms = 0;
-  hip_check(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
-
-  res->d_out = out_ptr;
-  res->out_len = out_len;
-  res->count = h_misc[1];   // every consensus read of a fast-path family is one record
-  for (int i = 0; i < FGX_STATS_LEN; i++) res->stats[i] = h_misc[i];
-  res->n_deferred = (uint32_t)(h_misc[29] & 0xFFFFFFFFull);
-  res->d_deferred = d_deferred.as<uint32_t>();
-  res->d_out_off = d_offsets.as<uint64_t>();
-  res->d_slot_size = d_sizes.as<uint64_t>();
-  res->n_slots = n_slots;
-  res->ms_kernels = ms;
-  float msf = 0, mse = 0;
-  hip_check(hipEventElapsedTime(&msf, ev[0], ev[1]), "elapsed");
-  hip_check(hipEventElapsedTime(&mse, ev[2], ev[3]), "elapsed");
-  res->ms_k_family = msf; res->ms_k_emit = mse;
-  last_packed_families = h_misc[40]; last_classic_families = h_misc[41];
-  res->cols_used = h_misc[28];
-  res->full_items = n_full;
-  return 0;
 }
 
 }  // namespace fgx

@@ -58,7 +58,7 @@ def background(head, n, seed=42):
 
 
 def chunk_starts(n_grp, n_rec, n_chunks):
-    """First group of each chunk after the first, as FastPath::run_once's split_geometry cuts the batch (fastpath.hip): families per wavefront
+    """First group of each chunk after the first, as Batch::set_up cuts the batch for the split pipeline (fastpath.hip): families per wavefront
     of the record kernel from the mean family size, chunks rounded up to whole workgroups (4 wavefronts) of it."""
     mean_recs = n_rec / n_grp
     fpw = min(16, max(1, int(64.0 / mean_recs))) if mean_recs >= 1.0 else 16

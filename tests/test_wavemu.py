@@ -1,6 +1,6 @@
 """The device-resident pipeline's WAVEFRONT kernels, executed on the CPU in 64-lane lock-step (the wave-level host emulator).
 
-tests/wavemu compiles fgumi_amd/csrc/fastpath.hip — FastPath::run_once and every kernel it launches (k_col_bound, k_split_parse, k_split_cols in
+tests/wavemu compiles fgumi_amd/csrc/fastpath.hip — the host driver (run_once, the stages of Batch) and every kernel it launches (k_col_bound, k_split_parse, k_split_cols in
 its builds, k_split_finish, k_simplex_seg, k_simplex_wave2, k_family_wave, k_deep_*, k_family, k_call_full, k_emit*) — for the host under
 tests/wavemu/simt.h: a fiber per thread, a rendezvous per cross-lane operation (__ballot, __shfl*, readlane, DPP, ds_bpermute, wave barriers,
 __syncthreads) evaluated with the hardware's semantics, LDS as arrays; everything else of the product's host side is tests/apiemu's (api.cpp

@@ -1,6 +1,6 @@
 // wavemu.cpp — TEST INFRASTRUCTURE ONLY.  Not part of the product, never loaded by it.
 //
-// fgumi_amd/csrc/fastpath.hip — the device-resident pipeline: FastPath::run_once and EVERY wavefront kernel it launches (k_col_bound,
+// fgumi_amd/csrc/fastpath.hip — the device-resident pipeline: its host driver (run_once, the stages of Batch) and EVERY wavefront kernel it launches (k_col_bound,
 // k_split_parse, k_split_cols in its three builds, k_split_finish, k_simplex_seg, k_simplex_wave2, k_family_wave, k_deep_*, k_family,
 // k_call_full, k_emit*, …) — compiled for the HOST under the 64-lane lock-step shim of simt.h, and linked with tests/apiemu's host side
 // (api.cpp unmodified, the fake HIP runtime, the host-compiled lane-per-item kernels) in place of apiemu's stand-in for the device
@@ -97,7 +97,7 @@ static inline int min(int a, int b) { return a < b ? a : b; }
 static inline int max(int a, int b) { return a > b ? a : b; }
 static inline unsigned long long min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 static inline unsigned long long max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-// ---- the runtime calls of FastPath::run_once that are macros / templates in the HIP headers ------------------------------------------------------
+// ---- the runtime calls of the host driver that are macros / templates in the HIP headers ------------------------------------------------------
 #define hipMemcpyFromSymbol(dst, sym, n, ...) (memcpy((dst), (const void*)(sym), (n)), hipSuccess)
 #define hipMemcpyToSymbol(sym, src, n, ...) (memcpy((void*)(sym), (src), (n)), hipSuccess)
 namespace hipcub {
