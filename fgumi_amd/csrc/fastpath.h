@@ -34,8 +34,10 @@ struct DuplexDesc {         // one duplex consensus record (slot 3g+1 = R1, 3g+2
   char rx[FAST_RX_CAP];
   uint8_t meth;             // methylation-aware mode (k_family_wave<1, 1>; in what was padding): bit 0 the AB-side strand's call was annotated, bit 1 the BA-side
                             // strand's, bit 2 a lone strand passed through is the BA one (is_ba_only: its tags are bm / bu / bt and its MM strand is G-m)
+  uint8_t capped;           // --max-reads-per-strand bit a read set of the molecule (k_family_wave<1, 0, 1>; padding too): the duplex error recount (cE / ce) reads the
+                            // counts over ALL source reads from col_obs_all, col_obs holds the counts of the scoring reads (depths)
 };
-static_assert(sizeof(DuplexDesc) == 96, "DuplexDesc: the methylation byte lies in the padding");
+static_assert(sizeof(DuplexDesc) == 96, "DuplexDesc: the methylation byte and the cap flag lie in the padding");
 // methylation-aware mode, duplex: what k_duplex_meth_sizes found for a record — the bytes of the standard record (the methylation tags follow them) and per
 // MM string (0 the AB-side strand's am / bm, 1 the BA-side strand's bm, 2 the duplex MM) its entries and the characters of its entries
 struct DuplexMethSlot { uint32_t std_size, n_hit[3], mm_len[3], _pad; };
@@ -168,6 +170,7 @@ struct FastParams {
   // duplex (k_family_wave<1>; with the methylation-aware mode k_family_wave<1, 1>, which fills meth_flag / meth_u / meth_t per column of the four read sets)
   uint32_t dmin_total, dmin_xy, dmin_yx; int64_t dmax_reads;
   uint32_t* col_obs;               // per column: observation counts of A,C,G,T, one byte each
+  uint32_t* col_obs_all;           // the same over every source read of the set, for the molecules a --max-reads-per-strand cap bites (allocated when the caller has a cap)
   DuplexDesc* dends;
   // CODEC (k_family_wave<2>)
   CodecDesc* cends; uint32_t cmin_reads, cmin_duplex_len; int64_t cmax_reads;
@@ -190,6 +193,7 @@ struct DuplexEmitParams {
   uint8_t per_base_tags; char cell0, cell1;
   uint32_t* n_slow;                // k_count_slow_duplex counts the valid records the fast writer leaves to the per-field kernel here (0: that kernel is not launched at all)
   const uint8_t* meth_flag;        // methylation-aware mode (the <1> builds of the writers): per column, the reference shows a cytosine of the strand's call
+  const uint32_t* col_obs_all;     // a caller with --max-reads-per-strand (the CAP builds of the writers): the recount source of the records with DuplexDesc::capped
 };
 
 struct CodecEmitParams {
@@ -217,7 +221,7 @@ struct FastPath {
   DevBuf d_ends, d_sizes, d_offsets, d_code, d_qual, d_depth, d_err, d_misc, d_deferred, d_out, d_scan_tmp, d_strings;
   uint32_t lds_tile_bytes = 12288;        // first launch: tiles of the common small families
   uint32_t lds_tile_bytes_large = 65536;  // workgroup-per-family kernel: raw records + unpacked base / quality tiles of one big family (2 workgroups per CU)
-  DevBuf d_retry, d_bound, d_colbase, d_statslots, d_full_items, d_full_count, d_obs, d_retry2, d_retry_old;
+  DevBuf d_retry, d_bound, d_colbase, d_statslots, d_full_items, d_full_count, d_obs, d_obs_all, d_retry2, d_retry_old;
   DevBuf d_w2img;                         // W2Lds image, built from the caller's tables at the first batch
   DevBuf d_famdesc;                       // k_col_bound's family descriptors
   DevBuf d_fwimg;                         // FwLds image (k_family_wave)

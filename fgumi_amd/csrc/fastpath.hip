@@ -33,7 +33,8 @@
 // Families the device does not decide are DEFERRED untouched to the general host path (simplex_host.cpp, duplex_host.cpp,
 // codec_host.cpp): reads with more than 6 CIGAR ops or SEQ / CIGAR length mismatch, unmapped reads, malformed records (so that
 // the general path raises the reference's fatal error), more than FAST_MAX_READS reads or more LDS than the launch provides,
-// duplex / CODEC molecules with indels or a biting per-strand read cap.  See DESIGN.md 4.
+// duplex / CODEC molecules with indels.  A per-strand read cap that bites is decided here (the CAP builds of k_family_wave<1> / <2> and of the
+// duplex record writers); deferred under one: a duplex cap of 0 and the methylation-aware duplex build.  See DESIGN.md 4.
 #if !defined(FGX_WAVEMU)      // (tests/wavemu compiles this file for the HOST under a 64-lane lock-step shim, with stand-ins for the runtime and the scans)
 #include <hipcub/hipcub.hpp>
 #endif
@@ -1108,7 +1109,10 @@ inline void build_fw_image(FwLds& L, const ConsensusTables& t) {
 
 // METH 1 (duplex only): the methylation-aware mode — per read set the anchor read's place on the reference, the unconverted / converted counts of every
 // column and converted bases read as unconverted ones before they are observed (see 6D); molecules with a record of more than one CIGAR op are deferred.
-template <int MODE, int METH = 0>
+// CAP 1 (duplex, METH 0): the build of a caller with --max-reads-per-strand — a read set above the cap is scored over its `cap` lowest name ranks, walked in
+// (rank, file order), and the observations of ALL its reads are counted beside them for the duplex error recount (see 5D / 6D); CAP 0 is the kernel without any of it.
+// CAP 1 (CODEC): the build of a caller with --max-reads-per-strand — the R1 list and the R2 list are cut to their `cap` lowest name ranks ahead of the geometry (5C).
+template <int MODE, int METH = 0, int CAP = 0>
 #ifndef FGX_WAVE_OCC_DUPLEX
 #define FGX_WAVE_OCC_DUPLEX 4   /* the duplex branch holds four column sets' worth of state beside the record lanes: at 5 waves per SIMD (96 VGPRs) its
                                    member loop spilled */
@@ -1849,6 +1853,15 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   // the four single-strand read sets: 0 = AB-R1, 1 = AB-R2, 2 = BA-R1, 3 = BA-R2
   unsigned long long em[4];
   em[0] = uniform_u64(amask & r1m & nzm); em[1] = uniform_u64(amask & r2m & nzm); em[2] = uniform_u64(bmask & r1m & nzm); em[3] = uniform_u64(bmask & r2m & nzm);
+  // --max-reads-per-strand (consensus_call, vanilla_caller.rs:706-779 with downsample_source_reads :970-980): a set above the cap is SCORED over its `cap`
+  // lowest fgbio name ranks — bases, qualities, depths and single-strand errors, and so the consensus length (the longest scoring read) and the coverage
+  // rules of 7D —, and the scoring reads enter the column in (rank, file order), not in file order.  Everything the reference computes from `source_reads`
+  // keeps the whole set: the duplex error recount (the all-reads counts of 6D) and the consensus UMI (8D works from em[]).  sm[k]: the scoring reads of
+  // set k; cap_ord: byte k of lane j holds the record that enters the columns of capped set k j-th.
+  unsigned long long sm[4] = {em[0], em[1], em[2], em[3]};
+  bool capped[4] = {false, false, false, false};
+  bool any_capped = false;
+  uint32_t cap_ord = 0;
   uint32_t elen[4], eoff[4];
   {
     bool cap_bites = false;
@@ -1856,10 +1869,27 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       if (P.dmax_reads >= 0 && (long long)__popcll(em[k]) > P.dmax_reads) cap_bites = true;
-      elen[k] = em[k] ? wave_max(((em[k] >> lane) & 1) ? final_len : 0) : 0;
+      if constexpr (CAP != 0) {
+        if (P.dmax_reads > 0 && (long long)__popcll(em[k]) > P.dmax_reads) {
+          const bool mine = (em[k] >> lane) & 1;
+          const int32_t rk = mine ? name_rank(W + lo + 32, name_len) : 0;
+          uint32_t before = 0;
+          for (unsigned long long m = em[k]; m; m &= m - 1) {
+            const uint32_t j = (uint32_t)__builtin_ctzll(m);
+            const int32_t rj = (int32_t)rlane((uint32_t)rk, j);
+            before += (rj < rk || (rj == rk && j < lane)) ? 1u : 0u;
+          }
+          sm[k] = uniform_u64(__ballot(mine && (long long)before < P.dmax_reads));
+          // (the positions of a set's reads are a permutation of 0 .. |set| - 1: every step's ballot holds exactly one lane)
+          for (uint32_t j = 0; j < (uint32_t)P.dmax_reads; j++) { const uint32_t r = (uint32_t)__builtin_ctzll(__ballot(mine && before == j)); if (lane == j) cap_ord |= r << (8 * k); }
+          capped[k] = true; any_capped = true;
+        }
+      }
+      elen[k] = sm[k] ? wave_max(((sm[k] >> lane) & 1) ? final_len : 0) : 0;
       eoff[k] = tot; tot += elen[k];
     }
-    if (cap_bites) { to_defer(); return; }                                 // --max-reads-per-strand that bites: name-rank downsampling on the host
+    // without the CAP build (the methylation-aware mode), and with a cap of 0 (no set has a consensus): the general path
+    if (cap_bites && (CAP == 0 || P.dmax_reads == 0)) { to_defer(); return; }
   }
   const uint32_t plen1 = (em[0] && em[3]) ? (elen[0] < elen[3] ? elen[0] : elen[3]) : 0;    // R1 duplex: AB-R1 with BA-R2
   const uint32_t plen2 = (em[1] && em[2]) ? (elen[1] < elen[2] ? elen[1] : elen[2]) : 0;    // R2 duplex: AB-R2 with BA-R1
@@ -1876,12 +1906,37 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   uint32_t dm_tr[4] = {0, 0, 0, 0}, dm_fu[4] = {0, 0, 0, 0};     // max depth over the paired (truncated) span / the whole strand
   bool odd_base = false;
   bool ann_set[4] = {false, false, false, false};                // methylation-aware mode: the set's call was annotated
+  // A capped set's columns once more, counting only: the observations of EVERY read of the set (the scoring ones included) under the masking rule of the
+  // column loops — what the duplex error recount of the record writers works from (duplex_consensus counts over source_reads, which the cap does not touch).
+  // The same number of passes in every lane: the cross-lane reads stay in wave-uniform control flow.
+  auto count_all = [&](unsigned long long all, uint32_t len_k, uint32_t off_k) {     // (by value: no dynamically indexed local array)
+    for (uint32_t p0 = 0; p0 < len_k; p0 += 64) {
+      const uint32_t p = p0 + lane;
+      const bool incol = p < len_k;
+      uint32_t cnt = 0;
+      for (unsigned long long m = all; m; m &= m - 1) {
+        const uint32_t r = (uint32_t)__builtin_ctzll(m);
+        const uint32_t x0 = rlane(d0, r), x1 = rlane(d1, r), x2 = rlane(d2, r);
+        const bool valid = incol && p < (x1 >> 16);
+        const bool rv = (x2 >> 16) != 0;
+        const uint32_t idx = valid ? (rv ? (x1 & 0xFFFF) - 1 - p : p) : 0;
+        const uint32_t bb = W[(x0 & 0xFFFF) + (idx >> 1)];
+        const uint32_t c = (bb >> ((~idx & 1) << 2)) & 15;
+        const uint32_t q = W[(x0 >> 16) + idx];
+        const uint32_t co = rv ? __builtin_bitreverse32(c) >> 28 : c;
+        const bool masked = p < (x2 & 0xFFFF) && q < min_bq;
+        if (valid && !masked && __popc(co) == 1) cnt += 1u << (8 * (uint32_t)__builtin_ctz(co));
+      }
+      if (incol) P.col_obs_all[col_base + off_k + p] = cnt;
+    }
+  };
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    const unsigned long long members = em[k];
+    const unsigned long long members = sm[k];                      // the scoring reads: the whole set unless the cap bites
     if (!members) continue;
     const uint32_t mc = (uint32_t)__popcll(members);
     const uint32_t plen = (k == 0 || k == 3) ? plen1 : plen2;
+    const bool by_rank = CAP != 0 && capped[k];                    // a capped set's reads enter a column in (rank, file order): cap_ord
     // Methylation-aware mode (annotate_and_normalize, vanilla_caller.rs:781-860; methylation.rs:193-242): the call's anchor is the LAST longest
     // source read of the set (max_by_key; file order = lane order), taken over all its reads — a cap that bites is deferred above.  Every read here
     // is one aligned block, so column p lies at the anchor's pos + p (forward) or at its last aligned base - p (reverse: the columns run in read
@@ -1931,6 +1986,9 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
 #ifdef FGX_DUPLEX_REQUIRE_REGULAR   /* measurement builds: a molecule with a set that is not regular is deferred — the bench line's deferred count says how many */
     if (mc > 1 && !regular) { to_defer(); return; }
 #endif
+#ifdef FGX_CAP_GENERAL_LOOP         /* measurement builds: a capped set takes the general loop below, the regular step serves file-order sets only (DESIGN.md 4 has the comparison) */
+    if (by_rank) regular = false;
+#endif
     if (regular) {
       const uint8_t* const pairs = (const uint8_t*)&sPair[0][0];
       for (uint32_t p0 = 0; p0 < elen[k]; p0 += 64) {
@@ -1948,9 +2006,13 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
           is_c = incol && ref_is_c(p);
           tcs = set_rev ? __builtin_bitreverse32(tcode) >> 28 : tcode; vcs = set_rev ? __builtin_bitreverse32(vcode) >> 28 : vcode;
         }
+        uint32_t nth = 0;
         for (unsigned long long m = members; m;) {
-          const uint32_t r = (uint32_t)__builtin_ctzll(m);
+          uint32_t r = (uint32_t)__builtin_ctzll(m);
           m &= m - 1;
+#ifndef FGX_CAP_GENERAL_LOOP
+          if constexpr (CAP != 0) { if (by_rank) r = (rlane(cap_ord, nth) >> (8 * k)) & 63u; nth++; }
+#endif
           const uint32_t x0 = rlane(d0, r), x1 = rlane(d1, r);
           const bool in = __builtin_amdgcn_inverse_ballot_w64(fw_lanes_below(x1 >> 16, (uint32_t)__builtin_amdgcn_readfirstlane((int)p0)));   // inside this member's final length
           const uint32_t q = W[iq + (x0 >> 16)];
@@ -1986,11 +2048,13 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
             P.col_code[o] = ob; P.col_qual[o] = oq; P.col_err[o] = (uint16_t)err;
           }
           P.col_obs[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24);
+          if constexpr (CAP != 0) { if (any_capped && !by_rank) P.col_obs_all[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24); }
           if constexpr (METH != 0) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; }
           dm_fu[k] = depth > dm_fu[k] ? depth : dm_fu[k];
           if (p < plen) dm_tr[k] = depth > dm_tr[k] ? depth : dm_tr[k];
         }
       }
+      if constexpr (CAP != 0) { if (by_rank) count_all(em[k], elen[k], eoff[k]); }
       continue;
     }
     // (a single-read set: the read's fields once, by every lane, ahead of the column loop — its trip count differs from lane to lane)
@@ -2018,8 +2082,10 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       } else {
         ChainAcc acc;                           // two Kahan chains while the column shows one base (consensus_math.h)
         acc.reset();
+        uint32_t nth = 0;
         for (unsigned long long m = members; m; m &= m - 1) {
-          const uint32_t r = (uint32_t)__builtin_ctzll(m);
+          uint32_t r = (uint32_t)__builtin_ctzll(m);
+          if constexpr (CAP != 0) { if (by_rank) r = (rlane(cap_ord, nth) >> (8 * k)) & 63u; nth++; }
           const uint32_t x0 = rlane(d0, r), x1 = rlane(d1, r), x2 = rlane(d2, r);
           bool valid = p < (x1 >> 16);
           const bool rv = (x2 >> 16) != 0;
@@ -2052,10 +2118,12 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         }
       }
       P.col_obs[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24);
+      if constexpr (CAP != 0) { if (any_capped && !by_rank) P.col_obs_all[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24); }
       if constexpr (METH != 0) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; }
       dm_fu[k] = depth > dm_fu[k] ? depth : dm_fu[k];
       if (p < plen) dm_tr[k] = depth > dm_tr[k] ? depth : dm_tr[k];
     }
+    if constexpr (CAP != 0) { if (by_rank) count_all(em[k], elen[k], eoff[k]); }
   }
   if (__any(odd_base)) { to_defer(); return; }
 #pragma unroll
@@ -2182,6 +2250,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         D->mi_off = (uint16_t)(fp_mi_lo - fp_lo); D->mi_len = (uint8_t)fp_mi_len;
         D->has_cb = fc_has_cb ? 1 : 0; D->cb_off = (uint16_t)(fc_cb_lo - fc_lo); D->cb_len = (uint8_t)fc_cb_len;
         D->has_rx = cnt > 0; D->rx_len = (uint8_t)ulen; D->type = (uint8_t)(1 + t); D->has_ba = O.has_ba ? 1 : 0;
+        if constexpr (CAP != 0) D->capped = any_capped ? 1 : 0;
         if constexpr (METH != 0) {   // which strands carry an annotation; a lone strand passed through keeps the BA side's tag names (duplex_caller.rs:1338-1398)
           auto ann_of = [&](uint32_t kk) { return kk == 0 ? ann_set[0] : kk == 1 ? ann_set[1] : kk == 2 ? ann_set[2] : ann_set[3]; };
           D->meth = (uint8_t)((ann_of(O.sa) ? 1u : 0u) | ((O.has_ba && ann_of(O.sb)) ? 2u : 0u) | ((!O.has_ba && O.sa >= 2) ? 4u : 0u));
@@ -2212,7 +2281,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   // after the strand combine and every record size is known here.
   // =====================================================================================================================
   // ---- 5C. templates: the partner of each record is the one other record with its read name ---------------------------------
-  uint32_t s_filtered = 0, rj_notfr = 0, rj_insuf = 0, rj_overlap = 0, rj_indel = 0, rj_clipfail = 0, s_cons = 0;
+  uint32_t s_filtered = 0, rj_notfr = 0, rj_insuf = 0, rj_overlap = 0, rj_indel = 0, rj_clipfail = 0, rj_down = 0, s_cons = 0;
   auto flush_stats = [&]() {
     if (lane == 0) {
       atomicAdd(&st[0], (unsigned long long)n);
@@ -2223,6 +2292,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       if (rj_overlap) atomicAdd(&st[3 + FGX_REJ_INSUFFICIENT_OVERLAP], (unsigned long long)rj_overlap);
       if (rj_indel) atomicAdd(&st[3 + FGX_REJ_INDEL_ERROR_BETWEEN_STRANDS], (unsigned long long)rj_indel);
       if (rj_clipfail) atomicAdd(&st[3 + FGX_REJ_CLIP_OVERLAP_FAILED], (unsigned long long)rj_clipfail);
+      if (rj_down) atomicAdd(&st[3 + FGX_REJ_DOWNSAMPLED], (unsigned long long)rj_down);
     }
   };
   {
@@ -2292,8 +2362,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   // ClippedRecordInfo (:1006-1040): hard clip at the 3' end; a reverse read loses its start and moves right
   const uint32_t clen = fr ? (l_seq > clip ? l_seq - clip : 0) : 0;                 // clipped_seq_len = reference span of the clipped M
   const unsigned long long adj = (unsigned long long)((long long)pos + 1) + (rev ? (clip < l_seq ? clip : l_seq) : 0);
-  const unsigned long long r1set = uniform_u64(__ballot(fr && first)), r2set = uniform_u64(__ballot(fr && !first));
-  const uint32_t n_strand = (uint32_t)__popcll(r1set | r2set);
+  unsigned long long r1set = uniform_u64(__ballot(fr && first)), r2set = uniform_u64(__ballot(fr && !first));
+  uint32_t n_strand = (uint32_t)__popcll(r1set | r2set);
   if (!r1set) { flush_stats(); return; }
   auto reject_all = [&](uint32_t& counter) { counter += n_strand; s_filtered += n_strand; flush_stats(); };
   if ((uint32_t)__popcll(r1set) < P.cmin_reads) { reject_all(rj_insuf); return; }
@@ -2302,13 +2372,33 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     const uint32_t l1ref = rlane(l_seq, (uint32_t)__builtin_ctzll(r1set)), l2ref = rlane(l_seq, (uint32_t)__builtin_ctzll(r2set));
     if (__any(fr && l_seq != (first ? l1ref : l2ref))) { to_defer(); return; }
   }
+  // --max-reads-per-strand (codec_caller.rs:765-802, cap_infos_to_lowest_ranking :1060-1072): after the alignment filter and the min-reads check, the
+  // R1 list and the R2 list each keep their `cap` lowest fgbio name ranks (ties in file order; the lists need not keep the same templates), the
+  // survivors stay in file order, and what is dropped is counted as Downsampled — never routed to --rejects.  Everything below sees the survivors only.
   if (P.cmax_reads >= 0) {
     if (P.cmax_reads == 0) { reject_all(rj_insuf); return; }
-    if ((long long)__popcll(r1set) > P.cmax_reads) { to_defer(); return; }       // the cap bites: name-rank downsampling on the host
+    if constexpr (CAP != 0) if ((long long)__popcll(r1set) > P.cmax_reads || (long long)__popcll(r2set) > P.cmax_reads) {
+      const int32_t rk = fr ? name_rank(W + lo + 32, name_len) : 0;
+      const unsigned long long mine = first ? r1set : r2set;                   // the list this lane's record is in
+      uint32_t before = 0;
+      for (unsigned long long m = r1set | r2set; m; m &= m - 1) {
+        const uint32_t j = (uint32_t)__builtin_ctzll(m);
+        const int32_t rj = (int32_t)rlane((uint32_t)rk, j);
+        before += (((mine >> j) & 1) && (rj < rk || (rj == rk && j < lane))) ? 1u : 0u;
+      }
+      const unsigned long long stay = uniform_u64(__ballot(fr && (long long)before < P.cmax_reads));
+      rj_down = n_strand - (uint32_t)__popcll(stay);
+      s_filtered += rj_down;
+      r1set &= stay; r2set &= stay; n_strand = (uint32_t)__popcll(stay);
+    }
+    // (the build without the cap never sees one — the launch pairs a cap with CAP 1 —; if it ever does, the general path decides the molecule)
+    if constexpr (CAP == 0) if ((long long)__popcll(r1set) > P.cmax_reads || (long long)__popcll(r2set) > P.cmax_reads) { to_defer(); return; }
   }
+  // this lane's record is a surviving R1 / R2 (CAP 0, the build of a caller without a cap: the FR records as they are)
+  const bool fr1 = CAP != 0 ? (bool)((r1set >> lane) & 1) : (fr && first), fr2 = CAP != 0 ? (bool)((r2set >> lane) & 1) : (fr && !first);
   // longest R1 / R2 by clipped reference length (first maximum)
-  const uint32_t mx1 = wave_max((fr && first) ? clen + 1 : 0), mx2 = wave_max((fr && !first) ? clen + 1 : 0);
-  const uint32_t L1 = (uint32_t)__builtin_ctzll(__ballot(fr && first && clen + 1 == mx1)), L2 = (uint32_t)__builtin_ctzll(__ballot(fr && !first && clen + 1 == mx2));
+  const uint32_t mx1 = wave_max(fr1 ? clen + 1 : 0), mx2 = wave_max(fr2 ? clen + 1 : 0);
+  const uint32_t L1 = (uint32_t)__builtin_ctzll(__ballot(fr1 && clen + 1 == mx1)), L2 = (uint32_t)__builtin_ctzll(__ballot(fr2 && clen + 1 == mx2));
   const bool r1_neg = (rlane(flags, L1) & bam::F_REVERSE) != 0, r2_neg = (rlane(flags, L2) & bam::F_REVERSE) != 0;
   const uint32_t adj_lo = (uint32_t)adj, adj_hi = (uint32_t)(adj >> 32);
   auto adj_of = [&](uint32_t r) { return ((unsigned long long)rlane(adj_hi, r) << 32) | rlane(adj_lo, r); };
@@ -2326,7 +2416,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   if (prp == 0 || nrp == 0) { reject_all(rj_indel); return; }
   if (prp + (long long)rl_n < nrp) { to_defer(); return; }                       // the general path raises the error
   const uint32_t cons_len = (uint32_t)(prp + (long long)rl_n - nrp);
-  const uint32_t len1 = wave_max((fr && first) ? clen : 0), len2 = wave_max((fr && !first) ? clen : 0);
+  const uint32_t len1 = wave_max(fr1 ? clen : 0), len2 = wave_max(fr2 ? clen : 0);
   if (cons_len < len1 || cons_len < len2) { reject_all(rj_clipfail); return; }
 
   PH(5)
@@ -3248,7 +3338,9 @@ __device__ __forceinline__ void duplex_combine(uint32_t ca, uint32_t qa, uint32_
   else { rb = ca; rq = FGX_MIN_PHRED; }
 }
 
-template <int METH>     // 1: the methylation-aware mode (the conversion-artifact rule in the strand combine)
+// CAP 1: the writers of a caller with --max-reads-per-strand — a record with DuplexDesc::capped takes the counts of the error recount (cE / ce) from
+// col_obs_all (every source read); depths (aD bD cD, ad bd) stay col_obs's (the scoring reads).  CAP 0: the writers without any of it.
+template <int METH, int CAP = 0>     // METH 1: the methylation-aware mode (the conversion-artifact rule in the strand combine)
 __global__ __launch_bounds__(256) void k_emit_duplex(DuplexEmitParams P) {
   const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(P.slot0 + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6)));
   const uint32_t lane = threadIdx.x & 63;
@@ -3279,8 +3371,10 @@ __global__ __launch_bounds__(256) void k_emit_duplex(DuplexEmitParams P) {
     const bool nocall = c.ca == 15 || c.cb == 15 || rq == FGX_MIN_PHRED;
     c.oc = nocall ? 15u : rb; c.oq = nocall ? (uint32_t)FGX_MIN_PHRED : rq;
     // errors: source reads of both strands that disagree with the raw duplex base (N never counts; a conversion event is no error)
-    const uint32_t agree = obs_of_code(oa, rb) + obs_of_code(ob, rb);
-    c.oe = (rb == 15 || artifact) ? 0u : (c.da + c.db) - agree;
+    uint32_t xa = oa, xb = ob;
+    if constexpr (CAP != 0) { if (D.capped) { xa = P.col_obs_all[a_off + i]; xb = P.col_obs_all[b_off + i]; } }
+    const uint32_t agree = obs_of_code(xa, rb) + obs_of_code(xb, rb);
+    c.oe = (rb == 15 || artifact) ? 0u : (obs_sum(xa) + obs_sum(xb)) - agree;
     return c;
   };
   // ---- reductions for aD aM aE / bD bM bE / cD cM cE -------------------------------------------------------------------------
@@ -3687,7 +3781,7 @@ __global__ __launch_bounds__(256) void k_count_slow_codec(const CodecDesc* __res
   const unsigned long long m = __ballot(slow);
   if (m && (threadIdx.x & 63) == 0) atomicAdd(n_slow, (uint32_t)__popcll(m));
 }
-template <int METH>     // 1: the methylation-aware mode (the conversion-artifact rule in the strand combine)
+template <int METH, int CAP = 0>     // METH 1: the methylation-aware mode (the conversion-artifact rule in the strand combine); CAP: see k_emit_duplex
 __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
   const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(P.slot0 + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6)));
   const uint32_t lane = threadIdx.x & 63;
@@ -3705,6 +3799,8 @@ __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
   // ---- every load of the record (indices clamped into the record's own segments, so unconditional) -----------------------
   uint32_t ca[DUP_SLOTS][2], qa[DUP_SLOTS][2], ea[DUP_SLOTS][2], oa[DUP_SLOTS][2], cb[DUP_SLOTS][2], qb[DUP_SLOTS][2], eb[DUP_SLOTS][2], ob[DUP_SLOTS][2];
   uint32_t rc[DUP_SLOTS];           // methylation-aware mode: either strand flags a reference cytosine, a byte per position of the pair
+  uint32_t na[DUP_SLOTS][2], nb[DUP_SLOTS][2];     // CAP: the recount's counts (every source read) of a capped record
+  const bool capped = CAP != 0 && D.capped != 0;
 #pragma unroll
   for (uint32_t t = 0; t < DUP_SLOTS; t++) {
     // (round 6) a lane's two neighbouring positions with ONE load per array and strand (2 + 2 + 4 + 8 bytes) instead of one per position: 16 vector memory
@@ -3719,6 +3815,14 @@ __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
     };
     ld2(a_off + pc, ca[t], qa[t], ea[t], oa[t]);
     ld2(b_off + pc, cb[t], qb[t], eb[t], ob[t]);
+    if constexpr (CAP != 0) {
+      na[t][0] = oa[t][0]; na[t][1] = oa[t][1]; nb[t][0] = ob[t][0]; nb[t][1] = ob[t][1];
+      if (capped) {
+        unsigned long long wa, wb;
+        __builtin_memcpy(&wa, (const uint8_t*)P.col_obs_all + 4 * (a_off + pc), 8); __builtin_memcpy(&wb, (const uint8_t*)P.col_obs_all + 4 * (b_off + pc), 8);
+        na[t][0] = (uint32_t)wa; na[t][1] = (uint32_t)(wa >> 32); nb[t][0] = (uint32_t)wb; nb[t][1] = (uint32_t)(wb >> 32);
+      }
+    }
     rc[t] = 0;
     if constexpr (METH != 0) { uint16_t fa, fb; __builtin_memcpy(&fa, P.meth_flag + a_off + pc, 2); __builtin_memcpy(&fb, P.meth_flag + b_off + pc, 2); rc[t] = (uint32_t)(fa | fb); }
   }
@@ -3741,7 +3845,8 @@ __global__ __launch_bounds__(256) void k_emit_duplex_fast(DuplexEmitParams P) {
         duplex_combine<METH>(xa, xq, xcb, xqb, ((rc[t] >> (8 * k)) & 0xFFu) != 0, rb, rq, artifact);
         const bool nocall = xa == 15 || xcb == 15 || rq == FGX_MIN_PHRED;
         oc = nocall ? 15u : rb; oq = nocall ? (uint32_t)FGX_MIN_PHRED : rq;
-        oe = (rb == 15 || artifact) ? 0u : (da + db) - (obs_of_code(oa[t][k], rb) + obs_of_code(ob[t][k], rb));
+        if constexpr (CAP != 0) oe = (rb == 15 || artifact) ? 0u : (obs_sum(na[t][k]) + obs_sum(nb[t][k])) - (obs_of_code(na[t][k], rb) + obs_of_code(nb[t][k], rb));
+        else oe = (rb == 15 || artifact) ? 0u : (da + db) - (obs_of_code(oa[t][k], rb) + obs_of_code(ob[t][k], rb));
       }
       w0[t][k] = ca[t][k] | (xcb << 4) | (oc << 8) | (qa[t][k] << 16) | (xqb << 24);
       w1[t][k] = da | (db << 8) | (ea[t][k] << 16) | (xeb << 24);
@@ -4000,7 +4105,7 @@ __global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, uns
 #define FGX_LAUNCH(kernel, grid, block, lds, st, ...) do { fp.last_launches++; hipLaunchKernelGGL((kernel), grid, block, lds, st, __VA_ARGS__); hip_check(hipGetLastError(), #kernel " launch"); } while (0)
 
 void FastPath::release() {
-  for (DevBuf* b : {&d_ends, &d_sizes, &d_offsets, &d_code, &d_qual, &d_depth, &d_err, &d_misc, &d_deferred, &d_out, &d_scan_tmp, &d_strings, &d_obs, &d_retry2,
+  for (DevBuf* b : {&d_ends, &d_sizes, &d_offsets, &d_code, &d_qual, &d_depth, &d_err, &d_misc, &d_deferred, &d_out, &d_scan_tmp, &d_strings, &d_obs, &d_obs_all, &d_retry2,
                     &d_retry, &d_bound, &d_colbase, &d_statslots, &d_full_items, &d_full_count, &d_retry_old, &d_w2img, &d_famdesc, &d_fwimg,
                     &d_split_rec, &d_split_fam, &d_split_out, &d_route, &d_s2img, &d_dir_size, &d_dir_off, &d_dir_base, &d_slot_desc, &d_slot_err, &d_out2, &d_scan_tmp2, &d_big, &d_deep_sizes, &d_deep_row0, &d_deep_rows, &d_deep_fams, &d_deep_out, &d_deep_out2, &d_mflag, &d_mu, &d_mt, &d_mslot, &d_mcontigs})
     b->free_();
@@ -4143,6 +4248,7 @@ struct Batch {
   // The duplex caller in the mode: the wavefront kernel's <1, 1> build annotates and normalises the four read sets of a molecule in its column
   // loops, the record writers' <1> builds apply the conversion-artifact rule, am/au/at, bm/bu/bt, MM/ML/cu/ct follow RX (duplex_meth.inc).
   const bool meth_dup = duplex && meth_on;
+  const bool dup_cap = duplex && !meth_on && o.duplex_max_reads_per_strand > 0;   // the CAP builds of k_family_wave<1> and of the duplex record writers
   // Simplex without --trim: which head of the launch chain?  Shallow families (the mean family fits a quarter of a wave's LDS
   // slice) start at k_simplex_seg<4>; everything else at the split pipeline (k_split_parse + k_split_cols, simplex_split.inc),
   // whose record kernel also leaves what k_col_bound would (column bound, byte-span descriptor).
@@ -4283,6 +4389,7 @@ struct Batch {
       fp.d_mslot.reserve((size_t)n_slots * (meth_dup ? sizeof(DuplexMethSlot) : sizeof(MethSlot)) + 64);
     }
     if (duplex) fp.d_obs.reserve(col_cap * 4); else fp.d_depth.reserve(col_cap * 2 + 64);
+    if (dup_cap) fp.d_obs_all.reserve(col_cap * 4);   // the all-reads counts of the molecules the cap bites: only a caller with a cap pays for them
   }
 
   // ---- the kernels' base parameters, the call_full pool, the retry lists ----
@@ -4303,6 +4410,7 @@ struct Batch {
       P.dmin_total = o.duplex_min_reads[0]; P.dmin_xy = o.duplex_min_reads[1]; P.dmin_yx = o.duplex_min_reads[2];
       P.dmax_reads = o.duplex_max_reads_per_strand;
       P.col_obs = fp.d_obs.as<uint32_t>(); P.dends = fp.d_ends.as<DuplexDesc>();
+      if (dup_cap) P.col_obs_all = fp.d_obs_all.as<uint32_t>();
     }
     if (codec) {    // single-strand caller of the CODEC caller (codec_caller.rs:374-397): min_reads 1, no cap, min consensus base quality 0
       P.min_reads = 1; P.max_reads = -1; P.min_cons_bq = 0; P.trim = 0; P.overlap = 0;
@@ -4350,6 +4458,8 @@ struct Batch {
       FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1>);
       FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<2>);
       FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1, 1>);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1, 0, 1>);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<2, 0, 1>);
       fp.lds_attr_set = true;
     }
     fp.d_retry2.reserve((size_t)n_grp * 4);
@@ -4588,8 +4698,10 @@ struct Batch {
     run_slices(st, !(duplex || codec), [&](const Slice& S, FastParams& PS) {
       const dim3 grid((n_cur + S.wpb - 1) / S.wpb), block(64 * S.wpb);
       const size_t lds = (size_t)S.wpb * S.bytes;
-      if (codec) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<2>), grid, block, lds, s, PS, n_cur);
+      if (codec && o.codec_max_reads_per_strand > 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<2, 0, 1>), grid, block, lds, s, PS, n_cur);
+      else if (codec) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<2>), grid, block, lds, s, PS, n_cur);
       else if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1, 1>), grid, block, lds, s, PS, n_cur);
+      else if (dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1, 0, 1>), grid, block, lds, s, PS, n_cur);
       else if (duplex) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1>), grid, block, lds, s, PS, n_cur);
       else FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<0>), grid, block, lds, s, PS, n_cur);
     });
@@ -4784,8 +4896,10 @@ struct Batch {
       DE.col_obs = P.col_obs;
       DE.n_slow = cnt(MISC_N_SLOW);
       DE.meth_flag = P.meth_flag;
+      DE.col_obs_all = P.col_obs_all;
       FGX_LAUNCH(k_count_slow_duplex, per_slot, dim3(256), 0, s, DE.ends, 0u, n_slots, DE.prefix_len, DE.rg_len, DE.n_slow);
       if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<1>), wave_per_slot, dim3(256), 0, s, DE);
+      else if (dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<0, 1>), wave_per_slot, dim3(256), 0, s, DE);
       else FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<0>), wave_per_slot, dim3(256), 0, s, DE);
     } else if (!direct || !dir_pure) {
       EmitParams E;
@@ -4817,6 +4931,7 @@ struct Batch {
     if ((duplex || codec) && (uint32_t)h_misc[MISC_N_SLOW] != 0) {     // records the fast writer left: the per-field kernel, then the counters again (the CODEC writer counts bases)
       if (codec) FGX_LAUNCH(k_emit_codec, wave_per_slot, dim3(256), 0, s, CE);
       else if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<1>), wave_per_slot, dim3(256), 0, s, DE);
+      else if (dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<0, 1>), wave_per_slot, dim3(256), 0, s, DE);
       else FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<0>), wave_per_slot, dim3(256), 0, s, DE);
       read_counters();
     }
