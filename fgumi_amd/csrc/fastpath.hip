@@ -4710,7 +4710,8 @@ struct Batch {
 
   // ---- deep families: k_deep_parse + k_deep_cols (simplex_deep.inc) take the big list; what is outside their shape goes on to k_family ----
   // One pass of the streaming kernels over a family list; returns how many families it handed on (to `out`).
-  // `size_class`: 0 = the wavefront-sized build of the record kernel (families of up to 64 records), 1 = two wavefronts (up to 128), 2 = four (up to DEEP_MAX)
+  // `size_class`: 0 = the wavefront-sized build of the record kernel (families of up to 64 records), 1 = two wavefronts (up to 128), 2 = four (up to DEEP_MAX),
+  // 3 = four, up to DEEP_CAP_MAX records (--max-reads: what the cap leaves of such a family fits an end's 255 reads)
   uint32_t deep_pass(const uint32_t* list, uint32_t n_list, int size_class, uint32_t* out) {
     fp.d_deep_sizes.reserve((size_t)n_list * 8 + 64); fp.d_deep_row0.reserve((size_t)n_list * 8 + 64);
     FGX_LAUNCH(k_deep_sizes, dim3((n_list + 255) / 256), dim3(256), 0, s, list, n_list, d_grp_first, fp.d_deep_sizes.as<uint64_t>());
@@ -4730,7 +4731,8 @@ struct Batch {
     PD.group_list = nullptr;
     if (size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64>), dim3(n_list), dim3(64), 0, s, PD, DP);
     else if (size_class == 1) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
-    else FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    else if (size_class == 2) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    else FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_CAP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
     if (meth_dev) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_cols<1>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
     else FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_cols<0>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
     uint32_t n_left = 0;
@@ -4766,6 +4768,12 @@ struct Batch {
       fp.d_deep_out2.reserve((size_t)n_more * 4 + 64);
       n_left = deep_pass(fp.d_deep_out.as<uint32_t>(), n_more, 2, fp.d_deep_out2.as<uint32_t>());
       big_list = fp.d_deep_out2.as<uint32_t>();
+      // --max-reads: a family of DEEP_MAX + 1 .. DEEP_CAP_MAX records fits the kernels once the cap has cut its ends; the large build handed those on
+      // (with what is not the kernels' shape, which the next build passes through)
+      if (n_left && P.max_reads >= 0) {
+        n_left = deep_pass(fp.d_deep_out2.as<uint32_t>(), n_left, 3, fp.d_deep_out.as<uint32_t>());   // (the first pass's list has been read: its room again)
+        big_list = fp.d_deep_out.as<uint32_t>();
+      }
     }
     fp.last_deep_families = meth_dev ? n_big : n_big - n_left;
     if (meth_dev) fp.last_meth_device = n_grp;

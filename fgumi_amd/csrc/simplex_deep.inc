@@ -22,14 +22,24 @@
 //                  the unanimous gate or an item for k_call_full; consensus UMI; record sizes (the cD / cM widths depend on the
 //                  depths), counters.
 //
-// Shape: k_simplex_wave2's record shape (simplex_wave2.inc), at most DEEP_MAX records, at most 255 retained reads per end; no family
-// with a fragment consensus AND a pair; --max-reads does not bite.  Everything else goes to k_family (up to 128 records) and from
-// there to the host path.
+// Shape: k_simplex_wave2's record shape (simplex_wave2.inc), at most DEEP_MAX records (DEEP_CAP_MAX under --max-reads), at most 255
+// retained reads per end; no family with a fragment consensus AND a pair.  Everything else goes to k_family (up to 128 records) and
+// from there to the host path.
+//
+// --max-reads (downsample_filtered_source_reads, vanilla_caller.rs:902-932) is decided in k_deep_parse where the family gates are taken,
+// with the counters and in the order of k_family_wave<0> and k_family (fastpath.hip): per end, after the zero-length reads are out and
+// the --min-reads checks, an end above the cap keeps its max_reads lowest fgbio name ranks (name_rank of the name in the blob, a thread
+// per record into `key`, whose pairing hash is done with; signed compare, ties in file order); the dropped reads get final length 0 —
+// "not retained" to every later step, so lengths, the min_reads-th-longest rule, rows, RX, cell barcode, orphan count and the methylation
+// anchor see the survivors only, in file order — and count as Downsampled (DeepFam::rej_down, flushed by k_deep_cols).  The overlap
+// pre-correction and its counters keep the whole family: a survivor's row may name a dropped mate, whose bytes are still in the blob.  The
+// limit of 255 reads per end applies after the cut.  The branch is workgroup-uniform: without a biting cap nothing of it runs.
 //
 // Reference semantics restated: the same as k_simplex_wave2 (vanilla_caller.rs:1080-1296, 1304-1422, 1454-1646, 1652-1755;
 // overlapping.rs:236-336, 627-684; raw-bam/overlap.rs:181-357; simple_umi.rs:46-117).
 
 constexpr uint32_t DEEP_MAX = 512;           // records per family (LDS arrays of k_deep_parse: 23 KB; an end holds at most 255 retained reads anyway)
+constexpr uint32_t DEEP_CAP_MAX = 1024;      // ... under --max-reads, which leaves an end at most max_reads of them (46 KB; `partner` stays 16 bits)
 
 struct DeepRow {            // 32 bytes: one retained read of an end — eight dwords, read through the scalar unit (one s_load_dwordx8; sub-dword
                             // fields of a struct would come through vector memory, one dependent round trip before the row's own loads)
@@ -50,7 +60,8 @@ struct DeepFam {            // 64 bytes
   // column p of the end lies at reference position a_ref0 + step * p of contig a_info & 0x0FFFFFFF
   int32_t a_ref0[2];
   uint32_t a_info[2];       // contig | annotated << 28 | step is -1 << 29 | is_top_strand(anchor) << 30 | is_top_strand(first retained read) << 31
-  uint32_t _pad[7];
+  uint32_t rej_down;        // retained reads that --max-reads dropped
+  uint32_t _pad[6];
 };
 static_assert(sizeof(DeepRow) == 32 && sizeof(DeepFam) == 96, "deep descriptors");
 
@@ -95,8 +106,9 @@ struct DeepLds {
   uint32_t clen[3];
 };
 
-// <NT, MAXR>: threads per workgroup and the records a family may have — <256, 512> for the families above 64 records, <64, 64> for
-// everything else when the streaming kernels are the whole pipeline (methylation-aware mode: a wavefront per family, 3 KB of LDS)
+// <NT, MAXR>: threads per workgroup and the records a family may have — <128, 128> and <256, 512> for the families above 64 records, <256, 1024>
+// for those of more than 512 under --max-reads (an end fits its 255 reads after the cut only), <64, 64> for everything else when the streaming
+// kernels are the whole pipeline (methylation-aware mode: a wavefront per family, 3 KB of LDS)
 template <uint32_t NT, uint32_t MAXR>
 __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
   constexpr uint32_t DEEP_NT = NT;
@@ -122,11 +134,14 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
   };
   // (first of all: a family that leaves for the deferred list — methylation-aware mode — is visited by no other kernel, and the slot tables are not cleared between batches)
   if (tid < 3) { P.ends[3 * g + tid].valid = 0; P.rec_sizes[3 * g + tid] = 0; }
-  if (n > MAXR && MAXR < DEEP_MAX) {                         // the build for larger families takes it (the host launches it over this list next)
+  // the build for larger families takes it (the host launches it over this list next): above DEEP_MAX records only under --max-reads — without a cap
+  // such a family has an end of more than 255 reads (almost always) — and the DEEP_CAP_MAX build, launched over what the DEEP_MAX build left, passes on what
+  // that build had to decide
+  if ((n > MAXR && (MAXR < DEEP_MAX || (MAXR < DEEP_CAP_MAX && n <= DEEP_CAP_MAX && P.max_reads >= 0))) || (MAXR > DEEP_MAX && n <= DEEP_MAX && !P.meth_mode)) {
     if (tid == 0) { F->status = 0; const uint32_t k = atomicAdd(D.n_out, 1u); D.out_list[k] = g; }
     return;
   }
-  if (n > DEEP_MAX || n == 0 || n < P.min_reads) { leave(); return; }   // (uniform; fewer records than --min-reads: k_family counts them, simplex.rs:673-683)
+  if (n > MAXR || n == 0 || n < P.min_reads) { leave(); return; }   // (uniform; fewer records than --min-reads: k_family counts them, simplex.rs:673-683)
   __syncthreads();
   const uint32_t min_bq = P.min_input_bq & 0xFFu;
 
@@ -330,8 +345,11 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
 
   // ---- 4. family gates (process_group :1329-1422, process_subgroup :1454-1646), as k_simplex_wave2 takes them ----------------------
   bool ok[3] = {false, false, false};
-  uint32_t rej_insuf = 0, rej_zero = 0, rej_orphan = 0;
+  uint32_t rej_insuf = 0, rej_zero = 0, rej_orphan = 0, rej_down = 0;
   bool bites = false, rank_rule = false;
+  bool cand[3] = {false, false, false}, cut[3] = {false, false, false};   // the end reaches the cap / the cap bites on it
+  uint32_t rem0[3] = {0, 0, 0};                              // retained reads of the end before the cut
+  bool capped = false;
   for (uint32_t e = 0; e < 3; e++) {
     const uint32_t cnt = S.cnt[e], rem = S.rem[e];
     if (cnt == 0) continue;
@@ -339,7 +357,49 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
     rej_zero += cnt - rem;
     if (rem < P.min_reads) { rej_insuf += rem; continue; }
     if (rem == 0) continue;
-    if (P.max_reads >= 0 && (long long)rem > P.max_reads) { bites = true; continue; }
+    cand[e] = true; rem0[e] = rem;
+    if (P.max_reads >= 0 && (long long)rem > P.max_reads) { cut[e] = true; capped = true; }
+  }
+  // --max-reads (downsample_filtered_source_reads :902-932, as k_family_wave<0> and k_family restate it): of an end above the cap the max_reads
+  // lowest fgbio name ranks stay, ties in file order, and the survivors keep their file order.  A dropped read becomes a read of final length 0:
+  // that is what "not retained" means to everything below (lengths, rows, UMIs, cell barcode, anchor), and its bytes stay where its mate's row
+  // finds them.  (Workgroup-uniform: a caller without a cap, or one whose cap does not bite, runs nothing of this.)
+  if (capped) {
+    for (uint32_t r = tid; r < n; r += DEEP_NT)              // (the pairing hash is done with: `key` holds the rank from here on)
+      if (cut[S.bits[r] & 3u] && S.final_len[r] > 0) S.key[r] = (uint32_t)name_rank(P.blob + S.off[r] + 32, S.name_len[r]);
+    __syncthreads();
+    uint32_t drop = 0;                                       // bit k: record tid + k * DEEP_NT is dropped
+    for (uint32_t r = tid, k = 0; r < n; r += DEEP_NT, k++) {
+      const uint32_t e = S.bits[r] & 3u;
+      if (!cut[e] || S.final_len[r] == 0) continue;
+      const int32_t rk = (int32_t)S.key[r];
+      uint32_t before = 0;
+      for (uint32_t j = 0; j < n; j++) {
+        if ((S.bits[j] & 3u) != e || S.final_len[j] == 0) continue;
+        const int32_t rj = (int32_t)S.key[j];
+        before += (rj < rk || (rj == rk && j < r)) ? 1u : 0u;
+      }
+      if ((long long)before >= P.max_reads) drop |= 1u << k;
+    }
+    if (tid == 0)                                            // (every thread read them for the gates above, a barrier ago)
+      for (uint32_t e = 0; e < 3; e++) if (cut[e]) { S.rem[e] = 0; S.fmin[e] = 0xFFFFFFFFu; S.fmax[e] = 0; }
+    __syncthreads();
+    for (uint32_t r = tid, k = 0; r < n; r += DEEP_NT, k++) {
+      const uint32_t e = S.bits[r] & 3u, fl = S.final_len[r];
+      if (!cut[e] || fl == 0) continue;
+      if ((drop >> k) & 1u) S.final_len[r] = 0;
+      else { atomicAdd(&S.rem[e], 1u); atomicMin(&S.fmin[e], fl); atomicMax(&S.fmax[e], fl); }
+    }
+    __syncthreads();
+  }
+  for (uint32_t e = 0; e < 3; e++) {
+    if (!cand[e]) continue;
+    const uint32_t rem = S.rem[e];
+    if (cut[e]) {
+      rej_down += rem0[e] - rem;
+      if (rem < P.min_reads) { rej_insuf += rem; continue; }   // (a cap below --min-reads)
+      if (rem == 0) continue;
+    }
     if (rem > 255u) { bites = true; continue; }             // (the per-chain observation counts of an item are bytes)
     ok[e] = true;
     if (S.fmin[e] != S.fmax[e] && P.min_reads > 1) rank_rule = true;
@@ -413,7 +473,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
     f.rx_cnt_a = (uint16_t)(ne ? S.rxcnt[end_a] : 0u); f.rx_cnt_b = (uint16_t)(ne == 2u ? S.rxcnt[2] : 0u);
     f.rx_len_a = (uint8_t)((ne && S.rxcnt[end_a]) ? S.rx_len[S.rxfirst[end_a]] : 0u);
     f.rx_len_b = (uint8_t)((ne == 2u && S.rxcnt[2]) ? S.rx_len[S.rxfirst[2]] : 0u);
-    f.rej_insuf = rej_insuf; f.rej_zero = rej_zero; f.rej_orphan = rej_orphan;
+    f.rej_insuf = rej_insuf; f.rej_zero = rej_zero; f.rej_orphan = rej_orphan; f.rej_down = rej_down;
     f.ov_agree = S.ov_agree; f.ov_dis = S.ov_dis; f.ov_corr = S.ov_corr;
     if (P.meth_mode && P.genome) {
       auto top_of = [&](uint32_t r) { return ((S.bits[r] & 4u) != 0) == ((S.bits[r] & 32u) != 0); };   // is_top_strand (methylation.rs:392-398): reverse == LAST
@@ -767,14 +827,15 @@ __global__ __launch_bounds__(256, FGX_DEEP_OCC) void k_deep_cols(FastParams P, D
   }
   if (lane == 0) {
     unsigned long long* st = P.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * 32;
-    const uint32_t s_insuf = Fp->rej_insuf, s_zero = Fp->rej_zero, s_orphan = Fp->rej_orphan;
+    const uint32_t s_insuf = Fp->rej_insuf, s_zero = Fp->rej_zero, s_orphan = Fp->rej_orphan, s_down = Fp->rej_down;
     const uint32_t ov_agree = Fp->ov_agree, ov_dis = Fp->ov_dis, ov_corr = Fp->ov_corr;
     atomicAdd(&st[0], (unsigned long long)n);
     if (ne) atomicAdd(&st[1], (unsigned long long)ne);
-    if (s_insuf + s_zero + s_orphan) atomicAdd(&st[2], (unsigned long long)(s_insuf + s_zero + s_orphan));
+    if (s_insuf + s_zero + s_orphan + s_down) atomicAdd(&st[2], (unsigned long long)(s_insuf + s_zero + s_orphan + s_down));
     if (s_insuf) atomicAdd(&st[3 + FGX_REJ_INSUFFICIENT_READS], (unsigned long long)s_insuf);
     if (s_zero) atomicAdd(&st[3 + FGX_REJ_ZERO_LENGTH_AFTER_TRIMMING], (unsigned long long)s_zero);
     if (s_orphan) atomicAdd(&st[3 + FGX_REJ_ORPHAN_CONSENSUS], (unsigned long long)s_orphan);
+    if (s_down) atomicAdd(&st[3 + FGX_REJ_DOWNSAMPLED], (unsigned long long)s_down);
     if (ov_agree + ov_dis) atomicAdd(&st[24], (unsigned long long)(ov_agree + ov_dis));
     if (ov_agree) atomicAdd(&st[25], (unsigned long long)ov_agree);
     if (ov_dis) atomicAdd(&st[26], (unsigned long long)ov_dis);
