@@ -31,10 +31,14 @@
 //   crates/fgumi-raw-bam/src/{overlap.rs:21-357, hash.rs:14-89, builder.rs:122-301, cigar.rs:404-500}
 //
 // Families the device does not decide are DEFERRED untouched to the general host path (simplex_host.cpp, duplex_host.cpp,
-// codec_host.cpp): reads with more than 6 CIGAR ops or SEQ / CIGAR length mismatch, unmapped reads, malformed records (so that
-// the general path raises the reference's fatal error), more than FAST_MAX_READS reads or more LDS than the launch provides,
+// codec_host.cpp): reads with more than 16 CIGAR ops or SEQ / CIGAR length mismatch, malformed records (so that
+// the general path raises the reference's fatal error), unmapped reads of the duplex / CODEC callers and of the methylation-aware mode, an unmapped
+// record that carries CIGAR ops, more than FAST_MAX_READS reads or more LDS than the launch provides,
 // duplex / CODEC molecules with indels.  A per-strand read cap that bites is decided here (the CAP builds of k_family_wave<1> / <2> and of the
-// duplex record writers); deferred under one: a duplex cap of 0 and the methylation-aware duplex build.  See DESIGN.md 4.
+// duplex record writers); deferred under one: a duplex cap of 0 and the methylation-aware duplex build.  The simplex kernels take unmapped records
+// (`fgumi group --allow-unmapped`): a read without a CIGAR, no mate clip, no overlap step; ends that are uniform by flag stay where a mapped family of their
+// shape runs, an end with mapped AND unmapped reads is k_family_wave<0>'s (drop_unmapped_if_any_mapped) — up to 64 records and without indel reads, else
+// deferred.  See DESIGN.md 3.
 #if !defined(FGX_WAVEMU)      // (tests/wavemu compiles this file for the HOST under a 64-lane lock-step shim, with stand-ins for the runtime and the scans)
 #include <hipcub/hipcub.hpp>
 #endif
@@ -297,6 +301,20 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { FGX_WAVE_REDUCE(v, 0u
 __device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) { for (int o = 32; o > 0; o >>= 1) { unsigned long long t = __shfl_xor(v, o); v = t > v ? t : v; } return v; }
 __device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) { for (int o = 32; o > 0; o >>= 1) { unsigned long long t = __shfl_xor(v, o); v = t < v ? t : v; } return v; }
 __device__ __forceinline__ uint8_t comp_code(uint8_t c) { return (uint8_t)((0xF7B3D591E6A2C480ULL >> (4 * (c & 15))) & 15); }
+// The overlap step skips a pair with an unmapped member (overlapping.rs:236-240), whatever ref_id / pos say — two unmapped mates at -1 / -1, or an
+// unmapped read placed at its partner's position, would show a full shared span.  The simplex record kernels find a pair's span behind
+// `ref_id == mate's ref_id`: an unmapped record `idx` (its index in the family) takes this value in place of its ref_id (which nothing else reads) —
+// below every reference id, different for any two records — so that the test fails without a second flag word travelling across lanes.
+__device__ __forceinline__ int32_t unmapped_ref_key(uint32_t idx) { return (int32_t)(0x80000000u | idx); }
+// Does an end (fragments / R1s / R2s) of the family hold unmapped AND mapped records?  drop_unmapped_if_any_mapped (vanilla_caller.rs:1206-1232) then
+// works from the final lengths: the streaming kernels hand such a family to k_family_wave<0>.  `bal(p)`: the family's part of a ballot (every lane takes part).
+template <class Bal>
+__device__ __forceinline__ bool mixed_unmapped_end(const bool act, const uint32_t flags, Bal&& bal) {
+  const auto all = bal(act), um = bal(act && (flags & bam::F_UNMAPPED));
+  const auto e0 = bal(act && !(flags & bam::F_PAIRED)), e1 = bal(act && (flags & bam::F_PAIRED) && (flags & bam::F_FIRST));
+  const auto e2 = all & ~(e0 | e1), mp = all & ~um;
+  return ((e0 & um) && (e0 & mp)) || ((e1 & um) && (e1 & mp)) || ((e2 & um) && (e2 & mp));
+}
 
 // unaligned LDS reads built from aligned dwords (v_alignbyte_b32)
 __device__ __forceinline__ uint32_t ldsw(const uint8_t* W, uint32_t o) { return *(const uint32_t*)(W + o); }
@@ -1247,8 +1265,12 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       // indels).  Such reads all simplify to (M, length) for the alignment filter; clips only shift query offsets.
       uint32_t ops[MAX_CIG_OPS];
       ops[0] = 0;
+      // simplex: an unmapped record is a read without a CIGAR (create_source_read :1080-1190 looks at nothing else of it) — one block of l_seq query
+      // bases, no clip against the mate, no part in the overlap step; ref_id / pos are never used (they may be -1 or the mate's values)
+      const bool unm = MODE == 0 && METH == 0 && (flags & bam::F_UNMAPPED) && n_cig == 0;
       if (!excluded) {
-        if ((flags & bam::F_UNMAPPED) || n_cig == 0 || l_seq == 0 || pos < 0) bad = true;
+        if (unm) { if (l_seq == 0) bad = true; m_len = l_seq; ref_id = unmapped_ref_key(lane); }
+        else if ((flags & bam::F_UNMAPPED) || n_cig == 0 || l_seq == 0 || pos < 0) bad = true;
         else if (n_cig == 1) {
           ops[0] = ld32u(W, lo + 32 + l_name);
           const uint32_t ty = ops[0] & 15;
@@ -1293,7 +1315,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         const bool okp = !(flags & bam::F_MATE_UNMAPPED) && ref_id == mref && rv != mrv;
         strand = (okp && ((long long)mpos + 1 < (long long)pos + 1 + ((long long)l_seq - 1))) ? 1u : 0u;   // `strand` doubles as frself here
       }
-      if (MODE != 2 && !bad && !excluded && !long_cigar) {
+      if (MODE != 2 && !bad && !excluded && !long_cigar && !unm) {
         // mate-overlap clip (raw-bam/overlap.rs:181-357).  Closed form when the MC tag is one M op and all
         // coordinates are in the ordinary range (no saturating arithmetic can trigger); general code otherwise.
         bool fastclip = false;
@@ -1532,7 +1554,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   PH(4)
   if constexpr (MODE == 0) {
   // ---- 5. family gates with ballots (process_group :1329-1422, process_subgroup :1454-1646) -----------------
-  uint32_t s_total = n, s_cons = 0, s_filtered = 0, s_sec = 0, s_insuf = 0, s_zero = 0, s_orphan = 0, s_down = 0;
+  uint32_t s_total = n, s_cons = 0, s_filtered = 0, s_sec = 0, s_insuf = 0, s_zero = 0, s_orphan = 0, s_down = 0, s_unm = 0;
   const uint32_t n_sec = (uint32_t)__popcll(__ballot(act && excluded));
   const uint32_t n_reads = n - n_sec;
   if (n_sec) { s_filtered += n_sec; s_sec = n_sec; }
@@ -1555,6 +1577,18 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       uint32_t rem = (uint32_t)__popcll(kept), zero = cnt - rem;
       if (zero) { s_filtered += zero; s_zero += zero; }
       if (rem < P.min_reads) { if (rem) { s_filtered += rem; s_insuf += rem; } continue; }
+      {
+        // drop_unmapped_if_any_mapped (:1206-1232), evaluated over the surviving source reads: an end that still holds a mapped read loses its
+        // unmapped ones (Unmapped); everything below — alignment filter, --min-reads / --max-reads, consensus length, RX, cell barcode, orphan rule —
+        // sees the mapped reads only, in file order.  An end whose mapped reads all trimmed to nothing keeps its unmapped reads.
+        const unsigned long long un_e = __ballot(((kept >> lane) & 1) && (flags & bam::F_UNMAPPED));
+        if (un_e != 0 && un_e != kept) {
+          const uint32_t dropped = (uint32_t)__popcll(un_e);
+          s_filtered += dropped; s_unm += dropped;
+          kept &= ~un_e; rem -= dropped;
+          if (rem < P.min_reads) { s_filtered += rem; s_insuf += rem; continue; }
+        }
+      }
       if (P.max_reads >= 0 && (long long)rem > P.max_reads) {
         // downsample_filtered_source_reads (:902-932): the max_reads lowest fgbio name ranks stay, ties in file order
         const int32_t rk = name_rank(W + lo + 32, name_len);
@@ -1632,13 +1666,16 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     if (k >= ne) break;
     const unsigned long long members = e_mem[k];
     const uint32_t mc = (uint32_t)__popcll(members);
-    for (uint32_t p = lane; p < e_len[k]; p += 64) {
+    // (a wave-uniform trip count: the member loop reads lanes and push_full takes ballots — every lane takes part in the last pass too, `in` says whether it has a column)
+    for (uint32_t p0 = 0; p0 < e_len[k]; p0 += 64) {
+      const uint32_t p = p0 + lane;
+      const bool in = p < e_len[k];
       uint8_t ob, oq;
       uint32_t depth, err;
       if (mc == 1) {   // single-read consensus: LUT keyed by the unclamped quality (:1677-1708)
         uint32_t r = (uint32_t)__builtin_ctzll(members);
         uint32_t code, q;
-        view(rlane(seq_lo, r), rlane(qual_lo, r), rlane(l_seq, r), (rlane(flags, r) & bam::F_REVERSE) != 0, rlane(trim_to, r), p, &code, &q);
+        view(rlane(seq_lo, r), rlane(qual_lo, r), rlane(l_seq, r), (rlane(flags, r) & bam::F_REVERSE) != 0, rlane(trim_to, r), in ? p : 0u, &code, &q);
         uint8_t adj = q < 94 ? T->single_input_quals[q] : 0;
         if (adj < P.min_cons_bq) { ob = 15; oq = FGX_MIN_PHRED; } else { ob = (uint8_t)code; oq = adj; }
         depth = code != 15 ? 1 : 0;
@@ -1672,9 +1709,9 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         depth = obs[0] + obs[1] + obs[2] + obs[3];
         uint64_t o = col_base + e_coloff[k] + p;
         uint32_t d16 = depth < 32767u ? depth : 32767u;
-        P.col_depth[o] = (uint16_t)d16;
-        push_full(!resolved, o, ll, obs);
-        if (!resolved) continue;           // code / qual / errors arrive from k_call_full
+        if (in) P.col_depth[o] = (uint16_t)d16;
+        push_full(in && !resolved, o, ll, obs);
+        if (!in || !resolved) continue;    // code / qual / errors arrive from k_call_full
         err = depth - (bi == 0 ? obs[0] : bi == 1 ? obs[1] : bi == 2 ? obs[2] : bi == 3 ? obs[3] : 0u);
         uint8_t code = bi >= 0 ? (uint8_t)(1u << bi) : 15;
         if (depth < P.min_reads) { ob = 15; oq = 0; }
@@ -1686,7 +1723,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       }
       uint32_t d16 = depth < 32767u ? depth : 32767u, e16 = err < 32767u ? err : 32767u;
       uint64_t o = col_base + e_coloff[k] + p;
-      P.col_code[o] = ob; P.col_qual[o] = oq; P.col_depth[o] = (uint16_t)d16; P.col_err[o] = (uint16_t)e16;
+      if (in) { P.col_code[o] = ob; P.col_qual[o] = oq; P.col_depth[o] = (uint16_t)d16; P.col_err[o] = (uint16_t)e16; }
     }
   }
 
@@ -1799,6 +1836,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     if (s_zero) atomicAdd(&st[3 + FGX_REJ_ZERO_LENGTH_AFTER_TRIMMING], (unsigned long long)s_zero);
     if (s_orphan) atomicAdd(&st[3 + FGX_REJ_ORPHAN_CONSENSUS], (unsigned long long)s_orphan);
     if (s_down) atomicAdd(&st[3 + FGX_REJ_DOWNSAMPLED], (unsigned long long)s_down);
+    if (s_unm) atomicAdd(&st[3 + FGX_REJ_UNMAPPED], (unsigned long long)s_unm);
     if (ov_bases) atomicAdd(&st[24], (unsigned long long)ov_bases);
     if (ov_agree) atomicAdd(&st[25], (unsigned long long)ov_agree);
     if (ov_dis) atomicAdd(&st[26], (unsigned long long)ov_dis);

@@ -165,15 +165,17 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
       const unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
       const unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
       const unsigned long long aux_off = qual_off + l_seq;
-      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != 1) odd = true;
+      // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>); the methylation-aware mode needs a position
+      const bool unm = (flags & bam::F_UNMAPPED) != 0;
+      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u) || (unm && P.meth_mode)) odd = true;
       else {
         name_len = l_name - 1;
-        ref_id = (int32_t)gld32(rec); pos = (int32_t)gld32(rec + 4);
+        ref_id = unm ? unmapped_ref_key(r) : (int32_t)gld32(rec); pos = (int32_t)gld32(rec + 4);   // (no shared span with an unmapped member, phase 2)
         seq_rel = (uint32_t)seq_off;
-        if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY | bam::F_UNMAPPED)) odd = true;
+        if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
         if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;   // counted, but in no end
-        if (pos < 0 || pos >= (1 << 30)) odd = true;
-        {
+        if (!unm) {
+          if (pos < 0 || pos >= (1 << 30)) odd = true;
           const uint32_t op = gld32(rec + 32 + l_name), t = op & 15;
           if (!(t == 0 || t == 7 || t == 8) || (op >> 4) != l_seq) odd = true;
         }
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
         has_rx = (ax.got & 4u) != 0; rx_rel = ax.pk_rx & 0xFFFF; rx_len = ax.pk_rx >> 16;
         has_cb = (ax.got & 8u) != 0; cb_rel = ax.pk_cb & 0xFFFF; cb_len = ax.pk_cb >> 16;
         if (r == 0 && (!has_mi || P.prefix_len + 1 + mi_len >= 255)) odd = true;   // fatal in the reference (vanilla_caller.rs:1897-1908, 1795-1797)
-        if (!odd && has_mc) {
+        if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
           // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are both one M op
           bool simple = false;
           int32_t ML = 0;
@@ -245,15 +247,25 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
       }
     }
     if (odd) S.bad = 1;
+    else if (flags & bam::F_UNMAPPED) atomicOr(&S.bad, 2u << ty);    // bits 1 - 3: the end holds an unmapped record
     const uint32_t pt = odd ? 0u : (flags & bam::F_FIRST) ? 1u : (flags & bam::F_LAST) ? 2u : 0u;   // pair-map type (overlapping.rs:627-684)
     S.off[r] = off; S.key[r] = (hash << 2) | pt; S.pos[r] = pos; S.ref_id[r] = ref_id;
     S.l_seq[r] = (uint16_t)l_seq; S.seq_rel[r] = (uint16_t)seq_rel; S.name_len[r] = (uint16_t)name_len; S.clip[r] = (uint16_t)clip; S.final_len[r] = 0;
     S.wo[r] = 0; S.mo[r] = 0; S.wc[r] = 0; S.partner[r] = -1;
     S.rx_rel[r] = (uint16_t)rx_rel; S.cb_rel[r] = (uint16_t)cb_rel; S.rx_len[r] = (uint8_t)rx_len; S.cb_len[r] = (uint8_t)cb_len;
-    S.bits[r] = (uint8_t)(ty | ((flags & bam::F_REVERSE) ? 4u : 0u) | (has_rx ? 8u : 0u) | (has_cb ? 16u : 0u) | ((flags & bam::F_LAST) ? 32u : 0u));
+    S.bits[r] = (uint8_t)(ty | ((flags & bam::F_REVERSE) ? 4u : 0u) | (has_rx ? 8u : 0u) | (has_cb ? 16u : 0u) | ((flags & bam::F_LAST) ? 32u : 0u) |
+                         ((flags & bam::F_UNMAPPED) ? 64u : 0u));
   }
   __syncthreads();
-  if (S.bad) { leave(); return; }
+  if (S.bad & 1u) { leave(); return; }
+  if (S.bad >> 1) {
+    // some record is unmapped (workgroup-uniform; a batch of mapped reads never comes here): bits 4 - 6, the end holds a mapped record.  An end with both
+    // is not this path's — drop_unmapped_if_any_mapped (:1206-1232) works from the final lengths, k_family_wave<0> decides it up to 64 records
+    for (uint32_t r = tid; r < n; r += DEEP_NT) if (!(S.bits[r] & 64u)) atomicOr(&S.bad, 16u << (S.bits[r] & 3u));
+    __syncthreads();
+    const uint32_t b = S.bad;
+    if ((b >> 1) & (b >> 4) & 7u) { leave(); return; }
+  }
 
   // ---- 2. pairs (pair map: per name the LAST R1-type and the LAST R2-type primary record; an R1 is paired unless a later R1 has its
   //         name) and the reference span each pair shares ----------------------------------------------------------------------------------
@@ -278,7 +290,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
         if (i + 8 > nl) { const unsigned long long mk = (1ULL << (8 * (nl - i))) - 1; wa &= mk; wb &= mk; }
         if (wa != wb) same = false;
       }
-      if (!same) { S.bad = 1; continue; }                   // equal hashes, different names: the exact rules live in k_family
+      if (!same) { atomicOr(&S.bad, 1u); continue; }        // equal hashes, different names: the exact rules live in k_family
       if (clater >= 0) continue;                            // a later R1 carries the name: this one is not paired
       const uint32_t b = (uint32_t)cmate;
       if (S.ref_id[a] != S.ref_id[b]) continue;
@@ -290,7 +302,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
       S.wo[b] = (uint16_t)o2; S.mo[b] = (uint16_t)o1; S.wc[b] = (uint16_t)cnt; S.partner[b] = (int16_t)a;
     }
     __syncthreads();
-    if (S.bad) { leave(); return; }
+    if (S.bad & 1u) { leave(); return; }
     // the overlapping-bases counters (overlapping.rs:51-60): a wavefront per pair, lane = shared position
     uint32_t ov_agree = 0, ov_dis = 0, ov_corr = 0;
     for (uint32_t a = wv; a < n; a += DEEP_NT / 64) {
@@ -504,8 +516,8 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
     const uint8_t* const rec0 = P.blob + S.off[0];
     AuxTags ax;
     {
-      const uint32_t l_name = rec0[8], l_seq0 = S.l_seq[0];
-      const uint32_t aux_off = 32u + l_name + 4u + ((l_seq0 + 1u) >> 1) + l_seq0;
+      const uint32_t l_seq0 = S.l_seq[0];
+      const uint32_t aux_off = (uint32_t)S.seq_rel[0] + ((l_seq0 + 1u) >> 1) + l_seq0;      // (seq_rel: behind the name and the CIGAR — one op, or none of an unmapped record)
       aux_walk(rec0, sTagCls, aux_off, P.rec_len[r0] - aux_off, P, ax);
     }
     E->col_off = P.col_base[g] + (k == 0 ? 0u : clen[end_a]);

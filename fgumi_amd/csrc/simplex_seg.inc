@@ -138,17 +138,18 @@ __global__ __launch_bounds__(256, FGX_SEG_OCC) void k_simplex_seg(FastParams P, 
     const uint32_t l_name = h2 & 0xFF, n_cig = h3 & 0xFFFF;
     l_seq = ld32u(W, lo + 16);
     flags = h3 >> 16;
-    const uint32_t seq_off = 32u + l_name + 4u;
-    if (l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != 1 || seq_off + (l_seq + 1) / 2 + l_seq > len) odd = true;
+    const bool unm = (flags & bam::F_UNMAPPED) != 0;          // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>)
+    const uint32_t seq_off = 32u + l_name + (unm ? 0u : 4u);
+    if (l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u) || seq_off + (l_seq + 1) / 2 + l_seq > len) odd = true;
     else {
       const uint32_t qual_off = seq_off + (l_seq + 1) / 2, aux_off = qual_off + l_seq;
       name_len = l_name - 1;
-      ref_id = (int32_t)ld32u(W, lo); pos = (int32_t)ld32u(W, lo + 4);
+      ref_id = unm ? unmapped_ref_key(sl) : (int32_t)ld32u(W, lo); pos = (int32_t)ld32u(W, lo + 4);
       seq_lo = lo + seq_off; qual_lo = lo + qual_off;
-      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY | bam::F_UNMAPPED)) odd = true;
+      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
       if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;   // counted, but in no end
-      if (pos < 0 || pos >= (1 << 30)) odd = true;
-      {
+      if (!unm) {
+        if (pos < 0 || pos >= (1 << 30)) odd = true;
         const uint32_t op = ld32u(W, lo + 32 + l_name), ty = op & 15;
         if (!(ty == 0 || ty == 7 || ty == 8) || (op >> 4) != l_seq) odd = true;
       }
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256, FGX_SEG_OCC) void k_simplex_seg(FastParams P, 
       has_mi = (ax.got & 2u) != 0; mi_lo = ax.pk_mi & 0xFFFF; mi_len = ax.pk_mi >> 16;
       has_rx = (ax.got & 4u) != 0; rx_lo = ax.pk_rx & 0xFFFF; rx_len = ax.pk_rx >> 16;
       has_cb = (ax.got & 8u) != 0; cb_lo = ax.pk_cb & 0xFFFF; cb_len = ax.pk_cb >> 16;
-      if (!odd && has_mc) {
+      if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
         // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are one M op each.
         // All terms are below 2^30 + 10^7 + 2^16: 32-bit signed arithmetic is exact.
         bool simple = false;
@@ -230,6 +231,8 @@ __global__ __launch_bounds__(256, FGX_SEG_OCC) void k_simplex_seg(FastParams P, 
   if (act && sl == 0 && (!has_mi || P.prefix_len + 1 + mi_len >= 255)) odd = true;   // fatal in the reference (vanilla_caller.rs:1897-1908, 1795-1797)
   if (act && !odd && W[qual_lo] == 0xFF) odd = true;                                  // absent qualities (:1119-1124): the first one decides here
   kill_old(fbal(odd) != 0);
+  act = alive && sl < n;
+  kill_old(mixed_unmapped_end(act, flags, fbal));         // drop_unmapped_if_any_mapped needs the final lengths: k_family_wave<0>'s
   act = alive && sl < n;
   const bool rev = (flags & bam::F_REVERSE) != 0;
   const uint32_t rxmask = fbal(act && has_rx), cbmask = fbal(act && has_cb);

@@ -196,6 +196,7 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
     bool has_mi = false, has_rx = false, has_cb = false;
     // fixed header: ref_id, pos, l_read_name | mapq | bin, n_cigar | flag ; l_seq, next ref, next pos, tlen
     const uint32_t l_name = hp[0].z & 0xFF, n_cig = hp[0].w & 0xFFFF;
+    const bool unm = live && ((hp[0].w >> 16) & bam::F_UNMAPPED);   // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>)
     uint32_t aux_rel = 0, aux_len = 0;
     if (live) {
       l_seq = hp[1].x;
@@ -203,7 +204,7 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
       const unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
       const unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
       const unsigned long long aux_off = qual_off + l_seq;
-      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != 1 || l_name + 4u > SP_HEAD) odd = true;   // (a name beyond the head window: rare, k_simplex_wave2's)
+      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u) || l_name + 4u > SP_HEAD) odd = true;   // (a name beyond the head window: rare, k_simplex_wave2's)
       else { aux_rel = (uint32_t)aux_off; aux_len = len - aux_rel; seq_rel = (uint32_t)seq_off; name_len = l_name - 1; }
     }
     const bool parse = live && !odd;
@@ -217,12 +218,12 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
     }
     wave_sync();
     if (parse) {
-      ref_id = (int32_t)hp[0].x; pos = (int32_t)hp[0].y;
-      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY | bam::F_UNMAPPED)) odd = true;
+      ref_id = unm ? unmapped_ref_key(lane) : (int32_t)hp[0].x; pos = (int32_t)hp[0].y;   // (no shared span with an unmapped member: `ov_cnt` stays 0 below)
+      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
       if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;   // counted, but in no end
       if (!(flags & bam::F_PAIRED) && (flags & (bam::F_FIRST | bam::F_LAST))) odd = true;  // a fragment for the caller, a mate for the overlap step
-      if (pos < 0 || pos >= (1 << 30)) odd = true;
-      {
+      if (!unm) {
+        if (pos < 0 || pos >= (1 << 30)) odd = true;
         const uint32_t op = ld32u(Wh, l_name), ty = op & 15;
         if (!(ty == 0 || ty == 7 || ty == 8) || (op >> 4) != l_seq) odd = true;
       }
@@ -236,7 +237,7 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
       has_mi = (ax.got & 2u) != 0; mi_rel = aux_rel + (ax.pk_mi & 0xFFFF); mi_len = ax.pk_mi >> 16;
       has_rx = (ax.got & 4u) != 0; rx_rel = aux_rel + (ax.pk_rx & 0xFFFF); rx_len = ax.pk_rx >> 16;
       has_cb = (ax.got & 8u) != 0; cb_rel = aux_rel + (ax.pk_cb & 0xFFFF); cb_len = ax.pk_cb >> 16;
-      if (!odd && has_mc) {
+      if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
         // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are one M op each
         bool simple = false;
         int32_t ML = 0;                                       // all terms below 2^30 + 10^7 + 2^16: 32-bit signed arithmetic is exact
@@ -406,6 +407,7 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
     // ---- family verdict -----------------------------------------------------------------------------------------------------------
     const bool f_odd = fbal(odd) != 0, f_coll = fbal(collide) != 0, f_irr = fbal(irregular) != 0, f_rxd = fbal(rx_diff) != 0;
     const bool f_frag = fbal(act && ty == 0u) != 0, f_pair = fbal(act && ty != 0u) != 0;
+    const bool f_mix = mixed_unmapped_end(act, flags, fbal);   // drop_unmapped_if_any_mapped needs the final lengths: k_family_wave<0>'s
     const bool rx_all = with_rx == nmask, rx_none = with_rx == 0;
     const uint32_t maxl = max_a > max_b ? max_a : max_b;
     // row strides of the family's LDS tile: reads up to 160 bases share ONE pair of strides (k_split_cols has a build with them as
@@ -413,7 +415,7 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
     const uint32_t qs = maxl <= 160u ? 160u : (maxl + 15u) & ~15u, ss = maxl <= 160u ? 80u : ((maxl + 1u) / 2u + 15u) & ~15u;
     const uint32_t qc = qs >> 4, sc = ss >> 4;
     const uint32_t need = n * (qs + ss);
-    bool take = !f_odd && !f_coll && !f_irr && !f_rxd && !(f_frag && f_pair) && (rx_all || rx_none) && n >= 1u && maxl >= 1u;
+    bool take = !f_odd && !f_coll && !f_irr && !f_rxd && !f_mix && !(f_frag && f_pair) && (rx_all || rx_none) && n >= 1u && maxl >= 1u;
     if (rx_all && rx0_len > (uint32_t)FAST_RX_CAP) take = false;
     if (P.max_reads >= 0 && ((long long)m_a > P.max_reads || (long long)m_b > P.max_reads)) take = false;   // --max-reads may bite: k_family_wave<0>
     if (need > 60000u || maxl > 4000u) take = false;

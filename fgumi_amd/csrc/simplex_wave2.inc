@@ -247,15 +247,16 @@ __global__ __launch_bounds__(256, FGX_V2_OCC) void k_simplex_wave2(FastParams P,
     const unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
     const unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
     const unsigned long long aux_off = qual_off + l_seq;
-    if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != 1) odd = true;
+    const bool unm = (flags & bam::F_UNMAPPED) != 0;          // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>)
+    if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u)) odd = true;
     else {
       name_len = l_name - 1;
-      ref_id = (int32_t)ld32u(W, lo); pos = (int32_t)ld32u(W, lo + 4);
+      ref_id = unm ? unmapped_ref_key(lane) : (int32_t)ld32u(W, lo); pos = (int32_t)ld32u(W, lo + 4);
       seq_lo = lo + (uint32_t)seq_off; qual_lo = lo + (uint32_t)qual_off;
-      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY | bam::F_UNMAPPED)) odd = true;
+      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
       if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;   // counted, but in no end
-      if (pos < 0 || pos >= (1 << 30)) odd = true;
-      {
+      if (!unm) {
+        if (pos < 0 || pos >= (1 << 30)) odd = true;
         const uint32_t op = ld32u(W, lo + 32 + l_name), ty = op & 15;
         if (!(ty == 0 || ty == 7 || ty == 8) || (op >> 4) != l_seq) odd = true;
       }
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(256, FGX_V2_OCC) void k_simplex_wave2(FastParams P,
       has_mi = (ax.got & 2u) != 0; mi_lo = ax.pk_mi & 0xFFFF; mi_len = ax.pk_mi >> 16;
       has_rx = (ax.got & 4u) != 0; rx_lo = ax.pk_rx & 0xFFFF; rx_len = ax.pk_rx >> 16;
       has_cb = (ax.got & 8u) != 0; cb_lo = ax.pk_cb & 0xFFFF; cb_len = ax.pk_cb >> 16;
-      if (!odd && has_mc) {
+      if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
         // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are both one M op
         // (k_family_wave<0> derives it; the general rules live there)
         bool simple = false;
@@ -337,6 +338,7 @@ __global__ __launch_bounds__(256, FGX_V2_OCC) void k_simplex_wave2(FastParams P,
   if (lane == 0 && (!has_mi || P.prefix_len + 1 + mi_len >= 255)) odd = true;   // fatal in the reference (vanilla_caller.rs:1897-1908, 1795-1797)
   if (act && !odd && W[qual_lo] == 0xFF) odd = true;                              // absent qualities (:1119-1124): the first one decides here
   if (__any(odd)) { to_old(); return; }
+  if (__any(act && (flags & bam::F_UNMAPPED)) && mixed_unmapped_end(act, flags, [](bool p) { return __ballot(p); })) { to_old(); return; }
   const bool cand = act;                  // no secondary / supplementary records in this shape
   const bool rev = (flags & bam::F_REVERSE) != 0;
   const unsigned long long rxmask = __ballot(cand && has_rx), cbmask = __ballot(cand && has_cb);

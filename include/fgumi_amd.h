@@ -162,7 +162,10 @@ int fgx_process_batch(fgx_caller* c, const uint8_t* records, uint64_t records_le
 /* Same contract with every input array already resident in HBM (device pointers) and the
  * consensus records left in HBM: the measured configuration of bench.py and the multi-GPU path.
  * `out->data` is a DEVICE pointer; `out->stats` is copied back (224 bytes).  Families the device
- * pipelines do not decide (reads with more than 6 CIGAR ops, unmapped reads, malformed records; for
+ * pipelines do not decide (reads with more than 16 CIGAR ops, malformed records; unmapped reads of the
+ * duplex / CODEC callers and of the methylation-aware mode — the simplex kernels take the unmapped records
+ * that `allow_unmapped` grouping keeps, deferring only an end that mixes mapped and unmapped reads in a
+ * family of more than 64 records or beside an indel read; for
  * duplex / CODEC also what the canonical form does not cover) are reported in
  * *n_deferred / d_deferred_groups and must be re-submitted through fgx_process_batch; 0 for
  * `simulate`-shaped input.  Duplex / CODEC molecules with indels or clips are canonicalised and decided in a second device pass
