@@ -7,7 +7,8 @@
 //           src/lib/commands/common.rs:384-397   consensus_pregroup_keep_flags (secondary / supplementary always dropped,
 //                                                 unmapped dropped unless --allow-unmapped)
 //           crates/fgumi-umi/src/lib.rs:370-375  extract_mi_base (duplex: cut the value at its last '/', if not leading)
-// Keys are compared as bytes (the reference compares `from_utf8_lossy` strings: identical for valid UTF-8 tag values).
+// Keys are compared as bytes (the reference compares `from_utf8_lossy` strings: identical for valid UTF-8 tag values), and as the ONE
+// string MI + '\t' + cell the reference builds: equal part lengths are the fast path, equal totals with another split the slow one.
 #ifndef FGX_DEVEMU            // (tests/apiemu compiles this file for the host with a serial scan)
 #include <hipcub/hipcub.hpp>
 #endif
@@ -86,7 +87,8 @@ __global__ void k_group_keys(const uint8_t* __restrict__ blob, uint64_t blob_len
     bam::Rec v{blob + off, len};
     const uint16_t f = v.flags();
     const bool flags_ok = !(f & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) && (o.allow_unmapped || !(f & bam::F_UNMAPPED));
-    const uint64_t aux = (uint64_t)v.aux_off();
+    // the aux offset in 64 bits, as aux_data_slice computes it (fields.rs:479-503): with an l_seq near 2^32 the 32-bit v.aux_off() wraps back into the record
+    const uint64_t aux = (uint64_t)v.seq_off() + ((uint64_t)v.l_seq() + 1) / 2 + (uint64_t)v.l_seq();
     if (flags_ok && aux <= len) {
       const uint32_t an = len - (uint32_t)aux;
       uint32_t vl = 0;
@@ -135,6 +137,14 @@ __global__ void k_group_bounds(const uint8_t* __restrict__ blob, const KeyLoc* _
         return true;
       };
       if (equal(A.mi_off, B.mi_off, B.mi_len) && equal(A.cb_off, B.cb_off, B.cb_len)) b = 0;
+    } else if ((uint64_t)A.mi_len + A.cb_len == (uint64_t)B.mi_len + B.cb_len) {
+      // The key is ONE string, MI + '\t' + cell (mi_group.rs:230-241): with a tab inside a value two keys can be equal with the parts split differently
+      // ("1\tA" + "" and "1" + "A\t").  Only with a cell tag configured (without one both cb_len are 0, and equal totals are equal mi_len): rare, byte by byte.
+      auto at = [&](const KeyLoc& L, uint64_t i) -> uint8_t { return i < L.mi_len ? blob[L.mi_off + i] : i == L.mi_len ? (uint8_t)'\t' : blob[L.cb_off + (i - L.mi_len - 1)]; };
+      const uint64_t total = (uint64_t)A.mi_len + A.cb_len + 1;
+      uint64_t i = 0;
+      while (i < total && at(A, i) == at(B, i)) i++;
+      if (i == total) b = 0;
     }
   }
   bound[k] = b;

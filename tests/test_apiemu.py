@@ -376,6 +376,19 @@ def test_boundaries_and_grouping_kernels_on_the_host():
     run_isolated("test_apiemu", "check_boundaries_and_grouping_kernels", env=env())
 
 
+def check_grouping_kernels_on_hostile_streams():
+    """tests/grouping_cases.py on grouping.hip compiled for the host: the tag walk behind every aux type, over malformed entries and at the
+    blob's last bytes, keys that differ in one place or only in where MI ends and the cell value begins, drops and groups across blocks and
+    scan calls of changing sizes, every layout of tests/layouts.py — each crafted case's hand-written answer against the oracle first, then
+    both entries against the oracle.  (tests/test_gpu_grouping.py runs the same checks on an MI355X.)"""
+    import grouping_cases
+    grouping_cases.check_everything_on_the_host_build()
+
+
+def test_grouping_kernels_on_hostile_streams_on_the_host():
+    run_isolated("test_apiemu", "check_grouping_kernels_on_hostile_streams", env=env())
+
+
 @pytest.mark.parametrize("resident", [0, 1])
 @pytest.mark.parametrize("defer", ["mod3", "indel"])
 def test_pipeline_resubmits_only_the_deferred_groups(defer, resident):
