@@ -1434,6 +1434,13 @@ void fgx_debug_last_split_builds(const fgx_caller* c, uint64_t* out4) {
   out4[0] = out4[1] = out4[2] = out4[3] = 0;
   if (c && c->fast) { const FastPath& f = c->fast->fp; out4[0] = f.last_packed_families; out4[1] = f.last_classic_families; out4[2] = f.last_split_build; out4[3] = f.last_first_stage_retries; }
 }
+// the packed build's families of the last device batch by row loop: out2[0] clean (every raw quality at or above --min-input-base-quality:
+// the loop reads no quality), out2[1] general
+void fgx_debug_last_packed_rows(const fgx_caller* c, uint64_t* out2) {
+  if (!out2) return;
+  out2[0] = out2[1] = 0;
+  if (c && c->fast) { out2[0] = c->fast->fp.last_packed_clean; out2[1] = c->fast->fp.last_packed_general; }
+}
 // the launch chain of the last device batch: out2[0] kernel launches of fastpath.hip's run_once (the scans of the library not counted), out2[1] host synchronisations in it
 void fgx_debug_last_chain(const fgx_caller* c, uint32_t* out2) { if (out2) { out2[0] = (c && c->fast) ? c->fast->fp.last_launches : 0u; out2[1] = (c && c->fast) ? c->fast->fp.last_host_syncs : 0u; } }
 uint32_t fgx_debug_last_routed(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_routed : 0u; }

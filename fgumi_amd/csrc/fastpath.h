@@ -158,7 +158,7 @@ struct FastParams {
   uint32_t lds_tile_bytes;
   uint32_t lds_wave_bytes;
   uint32_t s2_partner;             // k_split_cols<.., 1>: a <.., 2> launch over the same families follows (else it hands the families that are not its shape to the next launch)
-  uint32_t s2_packed;              // k_split_cols: 1 = ends of at least s2_nsafe rows try the packed pass first (round 5; FGX_S2_PACKED=0: measurements)
+  uint32_t s2_packed;              // k_split_cols: 1 = ends of at least s2_nsafe rows try the packed pass first (round 5; FGX_S2_PACKED=0: measurements); | 2: debug counters; | 4: the clean test (FGX_S2_CLEAN_ROWS=0: off)
   uint32_t s2_nsafe;               // k_split_cols: unanimous_cap_depth(tables, min_input_bq) — agreeing observations from which a column is the cap for certain (gate_core.h)
   FullItem* full_items; uint32_t* full_count; uint32_t full_cap;   // N_LISTS append lists of `full_cap` items each
   // methylation-aware mode on the streaming kernels (simplex_deep.inc; meth_mode = FGX_METHYLATION_*, 0: off): the genome of fgx_set_reference
@@ -233,6 +233,7 @@ struct FastPath {
   DevBuf d_mflag, d_mu, d_mt, d_mslot, d_mcontigs;   // methylation-aware mode: per-column annotation, per-slot tag sizes, the contig table
   uint32_t last_meth_device = 0;           // families of the last batch that the device pipeline decided in the methylation-aware mode
   uint32_t last_routed = 0;                // families the split pipeline handed to the k_simplex_wave2 chain in the last batch
+  uint64_t last_packed_clean = 0, last_packed_general = 0;        // ... of the packed build's: by its clean row loop (no quality read) / by its general one
   uint64_t last_packed_families = 0, last_classic_families = 0;   // families of the last batch finished by k_split_cols's packed build / by its classic builds (k_split_finish counts them)
   uint32_t last_split_build = 0;           // first-stage build of the last batch: 0 classic alone (or no split pipeline), 1 packed alone, 2 packed + partner launch
   uint32_t last_first_stage_retries = 0;   // families the first stage handed to the next launch

@@ -4170,7 +4170,7 @@ enum MiscWord : uint32_t {
   MISC_DIR_FLAGS = 36,       // direct records: low half families whose records differ in size from the prediction, high half records past the room
   MISC_N_BIG = 37,           // families of more than 64 records: k_family's list
   MISC_N_DEEP = 38,          // families a pass of the streaming kernels hands on
-  MISC_BUILD_FAMILIES = 40,  // [40, 44): the slots' diagnostics (k_reduce_stats): families finished by k_split_cols's packed build, by its classic builds
+  MISC_BUILD_FAMILIES = 40,  // [40, 44): the slots' diagnostics (k_reduce_stats): families finished by k_split_cols's packed build, by its classic builds, by the packed build's clean / general row loop
   MISC_N_SLOW = 44,          // duplex / CODEC: records the fast writer leaves to the per-field kernel
   MISC_READ_BACK = 46,       // words the end of a batch copies to the host
   MISC_WORDS = 48
@@ -4196,6 +4196,7 @@ struct ProcessSwitches {   // read once per process, at the first batch
   const int chunks = env_int(getenv("FGX_SPLIT_CHUNKS"), 0);             // >= 1: chunks of the split pipeline
   const int nosum = env_int(fgx_knob("FGX_S2_NOSUM"), 1);                // 0: every end through the f32 sums
   const int packed = env_int(getenv("FGX_S2_PACKED"), 1);                // 0: the 64-column passes only
+  const bool clean_rows = env_not0(getenv("FGX_S2_CLEAN_ROWS"));         // 0: the packed pass reads the qualities of every family (no clean test)
   const int s2_debug = env_int(fgx_knob("FGX_S2_DEBUG"), 0);
   const int pace = env_int(fgx_knob("FGX_S2_PACE"), 1);                  // 0: all record kernels up front
   const uint32_t s2_bytes = env_in(fgx_knob("FGX_S2_BYTES"), 2048, 32768, 0) & ~15u, s2_wpb = env_in(fgx_knob("FGX_S2_WPB"), 1, 4, 0);
@@ -4353,7 +4354,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
-    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
+    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
     fp.d_offsets.reserve(((size_t)n_slots + 1) * 8);
@@ -4440,7 +4441,7 @@ struct Batch {
     P.min_reads = o.min_reads; P.max_reads = o.max_reads;
     P.min_input_bq = o.min_input_base_quality; P.min_cons_bq = o.min_consensus_base_quality;
     // k_split_cols's sum-free observation step: from how many agreeing observations a column is the cap whatever their qualities (gate_core.h)
-    P.s2_packed = (ps.packed ? 1u : 0u) | ((ps.packed && ps.s2_debug) ? 2u : 0u);
+    P.s2_packed = (ps.packed ? 1u : 0u) | ((ps.packed && ps.s2_debug) ? 2u : 0u) | ((ps.packed && ps.clean_rows) ? 4u : 0u);
     P.s2_nsafe = ps.nosum ? unanimous_cap_depth(c->h_tables.t, (uint32_t)o.min_input_base_quality & 0xFFu, 64u) : FGX_NEVER_CAP;
     P.trim = o.trim; P.overlap = o.overlapping_consensus;
     if (duplex) {   // single-strand caller of the duplex caller (duplex_caller.rs:474-489): min_reads 1, min consensus base quality 2
@@ -4996,6 +4997,7 @@ struct Batch {
     res->n_slots = n_slots;
     res->ms_kernels = ms; res->ms_k_family = msf; res->ms_k_emit = mse;
     fp.last_packed_families = h_misc[MISC_BUILD_FAMILIES]; fp.last_classic_families = h_misc[MISC_BUILD_FAMILIES + 1];
+    fp.last_packed_clean = h_misc[MISC_BUILD_FAMILIES + 2]; fp.last_packed_general = h_misc[MISC_BUILD_FAMILIES + 3];
     res->cols_used = h_misc[MISC_COLS_USED];
     res->full_items = n_full;
   }

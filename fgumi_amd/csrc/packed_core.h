@@ -44,6 +44,24 @@ FGX_HD uint32_t bitrev32(uint32_t x) {
 #endif
 }
 
+// Two three-input boolean functions, one instruction each on gfx950 (v_bitop3_b32; byte of the truth table: a = 0xF0, b = 0xCC, c = 0xAA).  Spelled out
+// because the compiler, left alone, reassociates an OR chain over the rows (four instructions per word where two do) and shares x | b
+// between its two uses below (four where three do).
+FGX_HD uint32_t or_andn(uint32_t z, uint32_t t, uint32_t q) {      // z | (t & ~q)
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+  return __builtin_amdgcn_bitop3_b32(t, q, z, 0xBA);
+#else
+  return z | (t & ~q);
+#endif
+}
+FGX_HD uint32_t or_and(uint32_t x, uint32_t b, uint32_t c) {       // (x | b) & c
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+  return __builtin_amdgcn_bitop3_b32(x, b, c, 0xA8);
+#else
+  return (x | b) & c;
+#endif
+}
+
 // positions of the group at or past the end's read length are no columns: masks of the quality bytes that count (bit 7 of each)
 FGX_HD void count_masks(uint32_t lenE, uint32_t k, uint32_t* nfl, uint32_t* nfh) {
   *nfl = H; *nfh = H;
@@ -56,8 +74,18 @@ FGX_HD bool any_below(uint32_t qx, uint32_t qy, uint32_t mb4, uint32_t nfl, uint
   return ((((qx - mb4) & ~qx & nfl) | ((qy - mb4) & ~qy & nfh))) != 0u;
 }
 // the code nibbles to keep: 0xF where the position's quality is at or above the floor.  Bit 7 of each byte of gl / gh = "at or above"
-// (no borrow between bytes: q | 0x80 >= 128 >= floor; a quality >= 128 is above every floor this pass takes)
+// (no borrow between bytes: q | 0x80 >= 128 >= floor; a quality >= 128 is above every floor this pass takes).  Without a branch: two
+// byte permutes bring the flags of the even and of the odd positions into the order of the sequence bytes (byte i of a sequence word =
+// positions 2 i, high nibble, and 2 i + 1, low nibble), the odd ones move to bit 3, and (x << 1) - (x >> 3) widens bit 7 to 0xF0 and bit 3
+// to 0x0F in one subtraction (0x100 - 0x10, 0x10 - 0x01; the top byte's 0x100 falls off the word, as it should).
 FGX_HD uint32_t keep_mask(uint32_t qx, uint32_t qy, uint32_t mb4) {
+  const uint32_t gl = ((qx | H) - mb4) | qx, gh = ((qy | H) - mb4) | qy;
+  const uint32_t ev = perm(gh, gl, 0x06040200u), od = perm(gh, gl, 0x07050301u);
+  const uint32_t f = (ev & H) | ((od >> 4) & 0x08080808u);
+  return (f << 1) - (f >> 3);
+}
+// (the restatement bit by bit, as the pass ran up to round 6: tests/test_packed_rows_core.py holds the two against each other)
+FGX_HD uint32_t keep_mask_bitwise(uint32_t qx, uint32_t qy, uint32_t mb4) {
   const uint32_t gl = ((qx | H) - mb4) | qx, gh = ((qy | H) - mb4) | qy;
   uint32_t keep = 0;
   keep |= (uint32_t)((int32_t)(gl << 24) >> 31) & 0x000000F0u; keep |= (uint32_t)((int32_t)(gl << 16) >> 31) & 0x0000000Fu;
@@ -67,15 +95,38 @@ FGX_HD uint32_t keep_mask(uint32_t qx, uint32_t qy, uint32_t mb4) {
   return keep;
 }
 
+// CLEAN rows (round 7).  The only writer of qualities between staging and the column pass is the overlap correction, and it writes a
+// quality below the floor only together with code 0 (shared_base: `drop`); the clip phase only clears codes.  So a family whose RAW
+// qualities — at the positions below each read's own length — are all at or above the floor reaches the column pass with code 0 under
+// every sub-floor quality: b & keep_mask(q) == b for every row, and the row loop needs no quality at all (acc_row_seq).  The test, once
+// per family on the staged tile: a lane takes group k of its end and ORs (q - floor) & ~q over the end's rows; bit 7 of a byte is set
+// where the byte is below the floor; a borrow can only raise a false flag (or hide a true one) ABOVE a true one, and the length mask cuts
+// positions from the top: what it keeps of a word holds a flag exactly when it holds a byte below the floor.  Exact as a test of the group
+// for floors up to 128 (a byte of 128 and above is below no such floor); above 128 nothing is clean.
+struct Below { uint32_t lo, hi; };
+FGX_HD void below_reset(Below& z) { z.lo = 0; z.hi = 0; }
+FGX_HD void below_row(Below& z, uint32_t qx, uint32_t qy, uint32_t mb4) { z.lo = or_andn(z.lo, qx - mb4, qx); z.hi = or_andn(z.hi, qy - mb4, qy); }
+// rows of ONE length: the masks of count_masks(that length, k) once, behind the last row
+FGX_HD bool below_any(const Below& z, uint32_t nfl, uint32_t nfh) { return ((z.lo & nfl) | (z.hi & nfh)) != 0u; }
+// a row of its own length (a read shorter than its end's rows: what lies behind it in its last 16-byte chunk is tag text)
+FGX_HD void below_row_len(Below& z, uint32_t qx, uint32_t qy, uint32_t mb4, uint32_t l_seq, uint32_t k) {
+  uint32_t nfl, nfh;
+  count_masks(l_seq, k, &nfl, &nfh);
+  z.lo |= (qx - mb4) & ~qx & nfl; z.hi |= (qy - mb4) & ~qy & nfh;
+}
+
 struct Acc { uint32_t f_or, A8, B8; };     // OR of the codes (eight nibbles); 8 x the codes that are not 0 per byte: low nibbles, high nibbles
 FGX_HD void acc_reset(Acc& a) { a.f_or = 0; a.A8 = 0; a.B8 = 0; }
-// one row of the lane's group: q = its eight qualities (qx: positions 0 - 3), b = its eight codes
-FGX_HD void acc_row(Acc& a, uint32_t qx, uint32_t qy, uint32_t b, uint32_t mb4, uint32_t nfl, uint32_t nfh) {
-  if (any_below(qx, qy, mb4, nfl, nfh)) b &= keep_mask(qx, qy, mb4);
+// one row of the lane's group whose codes stand as they are (a clean family's): b = its eight codes
+FGX_HD void acc_row_seq(Acc& a, uint32_t b) {
   a.f_or |= b;
-  const uint32_t nz = (((b & 0x77777777u) + 0x77777777u) | b) & 0x88888888u;   // bit 3 of each nibble: the nibble is not 0
-  a.A8 += nz & 0x08080808u; a.B8 += (nz >> 4) & 0x08080808u;
+  const uint32_t x = (b & 0x77777777u) + 0x77777777u;                          // bit 3 of each nibble of x | b: the nibble is not 0
+  a.A8 += or_and(x, b, 0x08080808u); a.B8 += or_and(x, b, 0x80808080u) >> 4;
 }
+// one row of the lane's group: q = its eight qualities (qx: positions 0 - 3), b = its eight codes.  (Up to round 6 the clearing ran behind
+// any_below(.., nfl, nfh), a divergent block of 27 instructions for the whole wavefront as soon as one lane held a sub-floor quality —
+// every row of a family with overlapping mates; the masks no longer matter: codes at positions past the end are no columns.)
+FGX_HD void acc_row(Acc& a, uint32_t qx, uint32_t qy, uint32_t b, uint32_t mb4, uint32_t /*nfl*/ = 0, uint32_t /*nfh*/ = 0) { acc_row_seq(a, b & keep_mask(qx, qy, mb4)); }
 
 // What the lane's eight slots are: slot s = column c_lo + s of its end (forward end: position s of the group; reverse end: position
 // 7 - s, complemented).  code2 / qual2: a byte per slot; dep4: 16 bits per slot; flag2 / valid2: bit 7 of the slot's byte — flagged

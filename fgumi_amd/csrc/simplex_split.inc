@@ -823,9 +823,49 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   const uint32_t my_q = slot * QS, my_s = S0 + slot * SS;           // this record's rows
   if (__any(act && W[my_q] == 0xFF)) { to_route(); return; }        // absent qualities (vanilla_caller.rs:1119-1124): the general rules live further down the chain
   S2_ABLATE_AFTER(1, W[my_s])
+  const uint32_t min_bq = uni((uint32_t)P.min_input_bq & 0xFFu);
+
+  // ---- 1b. (packed build, round 7) CLEAN rows: is every raw quality of the family, at the positions below its read's own length, at or
+  //          above --min-input-base-quality?  Then every sub-floor quality the column pass meets was written by the overlap step below,
+  //          together with code 0 (`drop`), and the pass needs no quality at all (packed_core.h, acc_row_seq).  The layout is the column
+  //          pass's: a lane takes group k of its end, over ALL rows of both ends (known from SplitFam before the gates).  What lies at or
+  //          past l_seq is never looked at: the last 16-byte chunk of a quality row carries tag text, NULs included.
+  uint32_t dirty_v = 1u;          // per lane: its group holds a raw quality below the floor (or the test did not run).  A VECTOR register on purpose:
+                                  // the one bit is needed again in phase 6, and the scalar file is what this kernel is short of (its uniforms spill)
+  if constexpr (COLS == 1) {
+    if ((P.s2_packed & 4u) && min_bq <= 128u) {
+      const uint32_t ga = m_a ? (len_a + 7u) >> 3 : 0u, gb = m_b ? (len_b + 7u) >> 3 : 0u;      // (ga + gb <= 64: s2_packed_shape)
+      const bool inl = lane < ga + gb, in_b = inl && lane >= ga;
+      const uint32_t k = inl ? (in_b ? lane - ga : lane) : 0u;
+      const uint32_t rowE = in_b ? m_a : 0u, rows = inl ? (in_b ? m_b : m_a) : 0u;
+      const uint32_t m_lo = !m_b ? m_a : !m_a ? m_b : (m_a < m_b ? m_a : m_b), m_hi = m_a > m_b ? m_a : m_b;
+      const uint32_t mb4 = min_bq * 0x01010101u;
+      uint32_t qj = s2_mul24(rowE, QS) + 8u * k, j = 0;
+      pk::Below Z;
+      pk::below_reset(Z);
+      bool dirty;
+      if (__all(!act || l_seq == (ty == 2u ? len_b : len_a))) {
+        // every read as long as its end's rows (the usual family): the length masks once, behind the last row
+        for (; j + 4 <= m_lo; j += 4, qj += 4 * QS) {
+          const uint2 q0 = *(const uint2*)(W + qj), q1 = *(const uint2*)(W + qj + QS), q2 = *(const uint2*)(W + qj + 2 * QS), q3 = *(const uint2*)(W + qj + 3 * QS);
+          pk::below_row(Z, q0.x, q0.y, mb4); pk::below_row(Z, q1.x, q1.y, mb4); pk::below_row(Z, q2.x, q2.y, mb4); pk::below_row(Z, q3.x, q3.y, mb4);
+        }
+        for (; j < m_hi; j++, qj += QS) if (j < rows) { const uint2 q0 = *(const uint2*)(W + qj); pk::below_row(Z, q0.x, q0.y, mb4); }
+        uint32_t nfl, nfh;
+        pk::count_masks(in_b ? len_b : len_a, k, &nfl, &nfh);
+        dirty = pk::below_any(Z, nfl, nfh);
+      } else {
+        // reads of several lengths: each row with its own (the row table of the staging loop still stands)
+        for (; j < m_hi; j++, qj += QS)
+          if (j < rows) { const uint2 q0 = *(const uint2*)(W + qj); pk::below_row_len(Z, q0.x, q0.y, mb4, *(const uint32_t*)(W + ibase + 8u * (rowE + j) + 4u), k); }
+        dirty = pk::below_any(Z, pk::H, pk::H);
+      }
+      dirty_v = (inl && dirty) ? 1u : 0u;
+    }
+    FGX_PIN("+v"(dirty_v));
+  }
 
   // ---- 2. overlapping-bases pre-correction in LDS (overlapping.rs:236-336, 627-684) -------------------------------------------
-  const uint32_t min_bq = uni((uint32_t)P.min_input_bq & 0xFFu);
   uint32_t ov_agree = 0, ov_dis = 0, ov_corr = 0;             // (wave-uniform: counted with ballots)
   {
     // one shared base of a pair: o1 / o2 = sequence bytes, sh1 / sh2 = nibble shifts, q1 / q2 = quality bytes of the two reads.
@@ -973,7 +1013,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   // for it) —: every lane of the packed pass then stores all eight slots of its group with the wide stores, also the group that straddles
   // an end of its end (a reverse end's first columns, any end's last ones: for 150-base reads one lane of each end in EVERY family, which sent
   // every wavefront through the 4 + 2 + 1 store path as well); what it writes beside the end lands in the padding.  SplitOut.status bit 7
-  // tells k_split_finish which layout the family's EndDescs point into.
+  // tells k_split_finish which layout the family's EndDescs point into (bit 6, round 7: the packed pass ran its clean row loop).
   const uint32_t offA = COLS == 1 ? S2_PAD_FRONT : 0u, offB = COLS == 1 ? s2_padded_b(lc_a) : lc_a;
   // ---- 5b. DIRECT: where the family's records go and what they look like (all wave-uniform; vanilla_caller.rs:1767-1881) ---------
   S2DirRec RA, RB;
@@ -1318,21 +1358,26 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     const uint32_t rowE = in_b ? m_a : 0u;                      // first row of the lane's end
     const uint32_t qaddr0 = s2_mul24(rowE, QS) + 8u * k, saddr0 = S0 + s2_mul24(rowE, SS) + 4u * k;
     // (the arithmetic is packed_core.h's: the same functions run on the host in tests/test_packed_core.py)
-    const uint32_t H = pk::H;
-    uint32_t nfl, nfh;
-    pk::count_masks(lenE, k, &nfl, &nfh);
     const uint32_t mb4 = min_bq * 0x01010101u;
     pk::Acc A;
     pk::acc_reset(A);
-    {
+    if (!__any(dirty_v != 0u)) {
+      // CLEAN family (phase 1b): code 0 under every sub-floor quality already — the codes alone
+      uint32_t sj = saddr0, j = 0;
+      for (; j + 4 <= m; j += 4, sj += 4 * SS) {
+        const uint32_t b0 = *(const uint32_t*)(W + sj), b1_ = *(const uint32_t*)(W + sj + SS), b2_ = *(const uint32_t*)(W + sj + 2 * SS), b3_ = *(const uint32_t*)(W + sj + 3 * SS);
+        pk::acc_row_seq(A, b0); pk::acc_row_seq(A, b1_); pk::acc_row_seq(A, b2_); pk::acc_row_seq(A, b3_);
+      }
+      for (; j < m; j++, sj += SS) pk::acc_row_seq(A, *(const uint32_t*)(W + sj));
+    } else {
       uint32_t qj = qaddr0, sj = saddr0, j = 0;
       for (; j + 4 <= m; j += 4, qj += 4 * QS, sj += 4 * SS) {
         const uint2 q0 = *(const uint2*)(W + qj), q1 = *(const uint2*)(W + qj + QS), q2 = *(const uint2*)(W + qj + 2 * QS), q3 = *(const uint2*)(W + qj + 3 * QS);
         const uint32_t b0 = *(const uint32_t*)(W + sj), b1_ = *(const uint32_t*)(W + sj + SS), b2_ = *(const uint32_t*)(W + sj + 2 * SS), b3_ = *(const uint32_t*)(W + sj + 3 * SS);
-        pk::acc_row(A, q0.x, q0.y, b0, mb4, nfl, nfh); pk::acc_row(A, q1.x, q1.y, b1_, mb4, nfl, nfh);
-        pk::acc_row(A, q2.x, q2.y, b2_, mb4, nfl, nfh); pk::acc_row(A, q3.x, q3.y, b3_, mb4, nfl, nfh);
+        pk::acc_row(A, q0.x, q0.y, b0, mb4); pk::acc_row(A, q1.x, q1.y, b1_, mb4);
+        pk::acc_row(A, q2.x, q2.y, b2_, mb4); pk::acc_row(A, q3.x, q3.y, b3_, mb4);
       }
-      for (; j < m; j++, qj += QS, sj += SS) { const uint2 q0 = *(const uint2*)(W + qj); const uint32_t b0 = *(const uint32_t*)(W + sj); pk::acc_row(A, q0.x, q0.y, b0, mb4, nfl, nfh); }
+      for (; j < m; j++, qj += QS, sj += SS) { const uint2 q0 = *(const uint2*)(W + qj); const uint32_t b0 = *(const uint32_t*)(W + sj); pk::acc_row(A, q0.x, q0.y, b0, mb4); }
     }
     PH(9)
     // column order: slot s of the lane is column c_lo + s of its end (forward: position s of the group; reverse: position 7 - s, complemented)
@@ -1483,7 +1528,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   if (ires_asked) ires = ires_early;
   else if (icnt && lane == 0) ires = atomicAdd(&P.full_count[my_list], icnt);
   {
-    leave(COLS == 1 ? 0x81u : 1u, (ne << 8) | (type_a << 16) | (fk_a << 24), fk_b | (surv_a << 8) | (surv_b << 16) | (n << 24), lc_a | (lc_b << 16), rej, ov_agree, ov_dis);
+    leave(COLS == 1 ? (__any(dirty_v != 0u) ? 0x81u : 0xC1u) : 1u, (ne << 8) | (type_a << 16) | (fk_a << 24), fk_b | (surv_a << 8) | (surv_b << 16) | (n << 24), lc_a | (lc_b << 16), rej, ov_agree, ov_dis);
     if (lane == 0) ((uint32_t*)&P.split_out[g])[6] = ov_corr;
   }
   if constexpr (DIRECT != 0) {
@@ -1614,13 +1659,14 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63;
-  uint32_t c_total = 0, c_cons = 0, c_insuf = 0, c_zero = 0, c_orphan = 0, c_agree = 0, c_dis = 0, c_corr = 0, c_packed = 0, c_classic = 0;
+  uint32_t c_total = 0, c_cons = 0, c_insuf = 0, c_zero = 0, c_orphan = 0, c_agree = 0, c_dis = 0, c_corr = 0, c_packed = 0, c_classic = 0, c_clean = 0;
   if (gi < count) {
     const uint32_t g = P.group_list ? P.group_list[gi] : P.g0 + gi;
     const SplitOut O = P.split_out[g];
     const uint32_t slot0 = 3 * g;
-    const uint32_t o_status = O.status & 0x7Fu;
+    const uint32_t o_status = O.status & 0x3Fu;
     const bool padded = (O.status & 0x80u) != 0;   // finished by the packed build: its scratch layout (S2_PAD_FRONT / s2_padded_b)
+    const bool clean = (O.status & 0x40u) != 0;    // ... by its clean row loop (no quality read), else by the general one
     if (o_status == 2) { c_total = O.n; c_insuf = O.n; }
     const bool direct = P.out != nullptr;      // k_split_cols wrote the records (and the slots of the offset / size tables) itself: counters only
     if (o_status != 0 && !direct) {
@@ -1629,7 +1675,7 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
       P.rec_sizes[slot0] = 0; P.rec_sizes[slot0 + 1] = 0; P.rec_sizes[slot0 + 2] = 0;
     }
     if (o_status == 1) {
-      c_packed = padded ? 1u : 0u; c_classic = padded ? 0u : 1u;
+      c_packed = padded ? 1u : 0u; c_classic = padded ? 0u : 1u; c_clean = (padded && clean) ? 1u : 0u;
       c_total = O.n; c_cons = O.ne;
       c_insuf = O.rej & 0xFF; c_zero = (O.rej >> 8) & 0xFF; c_orphan = O.rej >> 16;
       c_agree = O.ov_agree; c_dis = O.ov_dis; c_corr = O.ov_corr;
@@ -1758,6 +1804,7 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
   const uint32_t t_cons = wave_sum(c_cons), t_total = wave_sum(c_total), t_insuf = wave_sum(c_insuf), t_zero = wave_sum(c_zero), t_orphan = wave_sum(c_orphan);
   const uint32_t t_agree = wave_sum(c_agree), t_dis = wave_sum(c_dis), t_corr = wave_sum(c_corr);
   const uint32_t t_packed = wave_sum(c_packed), t_classic = wave_sum(c_classic);   // (diagnostics, fgx_debug_last_split_builds: which build finished how many families)
+  const uint32_t t_clean = wave_sum(c_clean);                                       // (fgx_debug_last_packed_rows: the packed build's families by row loop)
   if (lane == 0) {
     unsigned long long* st = P.stats + (size_t)((blockIdx.x * 4 + (threadIdx.x >> 6)) & (STAT_SLOTS - 1)) * 32;
     if (t_total) atomicAdd(&st[0], (unsigned long long)t_total);
@@ -1773,5 +1820,7 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
     if (t_corr) atomicAdd(&st[27], (unsigned long long)t_corr);
     if (t_packed) atomicAdd(&st[28], (unsigned long long)t_packed);
     if (t_classic) atomicAdd(&st[29], (unsigned long long)t_classic);
+    if (t_clean) atomicAdd(&st[30], (unsigned long long)t_clean);
+    if (t_packed - t_clean) atomicAdd(&st[31], (unsigned long long)(t_packed - t_clean));
   }
 }
