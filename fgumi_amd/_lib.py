@@ -193,6 +193,10 @@ def load():
     L.fgx_host_libm_array.restype = None
     L.fgx_debug_last_deferral.argtypes = [VP, VP]
     L.fgx_debug_last_deferral.restype = None
+    L.fgx_debug_last_meth_device.argtypes = [VP]
+    L.fgx_debug_last_meth_device.restype = U32
+    L.fgx_debug_last_meth_clipped.argtypes = [VP]
+    L.fgx_debug_last_meth_clipped.restype = U32
     L.fgx_set_general_only.argtypes = [VP, I]
     L.fgx_set_general_only.restype = None
     L.fgx_set_fast_lds_bytes.argtypes = [VP, U32]

@@ -333,6 +333,12 @@ class _HandleCaller(ConsensusCaller):
         if rc != 0:
             raise RuntimeError(lib.fgx_last_error(self._h).decode())
 
+    def last_methylation_device_counts(self) -> dict:
+        """Diagnostics of the last device batch in the methylation-aware mode: `on_device` = families / molecules the device-resident
+        pipeline ran in the mode (0: the batch took the general path), `clipped` = those of them that held a soft- / hard-clipped
+        record (more than one CIGAR op) and were decided by the device kernels."""
+        return dict(on_device=int(lib.fgx_debug_last_meth_device(self._h)), clipped=int(lib.fgx_debug_last_meth_clipped(self._h)))
+
     def set_general_only(self, on: bool = True):
         """Route every family through the general host-orchestrated path (default: device-resident fast
         path, general path only for the families it defers)."""

@@ -1425,6 +1425,9 @@ uint32_t fgx_debug_last_split_chunks(const fgx_caller* c) { return (c && c->fast
 // pipeline handed down the k_simplex_wave2 chain
 uint32_t fgx_debug_last_big_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_big_families : 0u; }
 uint32_t fgx_debug_last_meth_device(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_meth_device : 0u; }
+// ... of which held a record of more than one CIGAR op (soft / hard clips around one aligned block) and were decided by the device kernels — counted
+// there, read back with the batch's other counters
+uint32_t fgx_debug_last_meth_clipped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_meth_clipped : 0u; }
 uint32_t fgx_debug_last_deep_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_families : 0u; }
 // the split pipeline's first stage in the last device batch: out4[0] families finished by k_split_cols's packed build, [1] by its classic builds
 // (k_split_finish counts both), [2] the build launched first (0 classic alone / no split pipeline, 1 packed alone, 2 packed + partner launch),

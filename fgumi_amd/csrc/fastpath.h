@@ -232,6 +232,7 @@ struct FastPath {
   DevBuf d_deep_sizes, d_deep_row0, d_deep_rows, d_deep_fams, d_deep_out, d_deep_out2;
   DevBuf d_mflag, d_mu, d_mt, d_mslot, d_mcontigs;   // methylation-aware mode: per-column annotation, per-slot tag sizes, the contig table
   uint32_t last_meth_device = 0;           // families of the last batch that the device pipeline decided in the methylation-aware mode
+  uint32_t last_meth_clipped = 0;          // ... of which held a record of more than one CIGAR op (clips around one aligned block) and were not deferred
   uint32_t last_routed = 0;                // families the split pipeline handed to the k_simplex_wave2 chain in the last batch
   uint64_t last_packed_clean = 0, last_packed_general = 0;        // ... of the packed build's: by its clean row loop (no quality read) / by its general one
   uint64_t last_packed_families = 0, last_classic_families = 0;   // families of the last batch finished by k_split_cols's packed build / by its classic builds (k_split_finish counts them)

@@ -90,6 +90,12 @@ constexpr uint32_t WG_CIG_OPS = 16;
 constexpr int WG_MC_OPS = 17;
 constexpr uint32_t COL_BOUND_PAD = 48;   // columns on top of a family's column bound: the padding of the packed build's scratch layout (simplex_split.inc, round 6)
 constexpr int STAT_SLOTS = 1024;        // spread the per-batch counters over many addresses (atomic contention)
+// Methylation-aware mode: families / molecules with a record of more than one CIGAR op that the device kernels decided (fgx_debug_last_meth_clipped).
+// The counter is the word of d_misc behind the deferred count (MISC_N_METH_CLIPPED == MISC_N_DEFERRED + 1, asserted at the enum) and is reached from
+// that pointer: a further member of FastParams would move the arguments of every kernel that takes one, the builds that count nothing included.
+// This holds only while P.n_deferred points at the low half of that 8-byte word of d_misc (fill_params sets it so; a u32 counter uses its word's low
+// half, so the next word's counter is two uint32_t further): whoever points n_deferred elsewhere gives this counter a FastParams member of its own.
+__device__ __forceinline__ uint32_t* meth_clipped_counter(const FastParams& P) { return P.n_deferred + 2; }
 
 struct ReadInfo {          // LDS, one per record of the family
   uint64_t goff;           // record body offset in the blob
@@ -1243,6 +1249,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   bool long_cigar = false;          // simplex: more CIGAR ops than MAX_CIG_OPS — nothing below may index `ops` by them
   bool cplx = false;                // simplex: a CIGAR with I / D / N / P ops — the family goes to the workgroup-per-family kernel
   uint32_t lead_s = 0, m_len = 0;   // query offset of the first aligned base, length of the aligned block
+  uint32_t tot_len = 0;             // (METH) the lengths of all the read's ops, hard clips included: the one M op simplify_cigar_from_raw makes of it
+  bool multi = false;               // (METH) the record has more than one CIGAR op
   uint32_t strand = 0;   // duplex: 1 = MI ends in /A, 2 = /B
   if (act) {
     const uint32_t h2 = ld32u(W, lo + 8), h3 = ld32u(W, lo + 12);
@@ -1259,7 +1267,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       seq_lo = lo + (uint32_t)seq_off; qual_lo = lo + (uint32_t)qual_off;
       excluded = (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) != 0;
       if (MODE == 1 && excluded) bad = true;   // the duplex caller has no secondary/supplementary filter: general path
-      if (METH != 0 && n_cig != 1) bad = true;   // methylation-aware mode: column p of a read set lies at the anchor's pos + p (or its end - p) only when the read is one aligned block
+      // (methylation-aware mode: column p of a read set lies at the anchor's pos + p, or at pos + T - 1 - p, only when the reference makes ONE M op of the
+      // read — clips around one aligned block, decided below; an indel read sends the molecule to the general path)
       if (MODE == 2 && (excluded || !(flags & bam::F_PAIRED))) bad = true;   // CODEC: fragments / non-primary records take the general path
       // CIGAR: one aligned block of M/=/X ops, optionally between soft / hard clips (what an aligner gives a read without
       // indels).  Such reads all simplify to (M, length) for the alignment filter; clips only shift query offsets.
@@ -1276,6 +1285,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
           const uint32_t ty = ops[0] & 15;
           if (!(ty == 0 || ty == 7 || ty == 8) || (ops[0] >> 4) != l_seq) bad = true;
           m_len = l_seq;
+          if constexpr (METH != 0) tot_len = l_seq;
         } else if (MODE != 2 && n_cig <= MAX_CIG_OPS) {
           uint32_t phase = 0, trail_s = 0;          // 0: leading clips, 1: aligned block, 2: trailing clips
           bool okc = true;
@@ -1284,6 +1294,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
             if (i >= n_cig) break;
             const uint32_t o = ld32u(W, lo + 32 + l_name + 4 * i), t = o & 15, ln = o >> 4;
             ops[i] = o;
+            if constexpr (METH != 0) { tot_len += ln; multi = true; }
             if (t == 0 || t == 7 || t == 8) { if (phase == 2) okc = false; phase = 1; m_len += ln; }
             else if (t == 4) { if (phase == 0) lead_s += ln; else { phase = 2; trail_s += ln; } }
             else if (t == 5) { if (phase == 1) phase = 2; }
@@ -1291,6 +1302,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
           }
           if (cplx && MODE == 0) { /* decided below: the whole family moves to the workgroup-per-family kernel */ }
           else if (!okc || m_len == 0 || m_len > 65535 || (unsigned long long)lead_s + m_len + trail_s != l_seq) bad = true;
+          if (METH != 0 && tot_len > 65535u) bad = true;
         } else if (MODE == 0 && n_cig <= WG_CIG_OPS) { cplx = true; long_cigar = true; }   // (more ops than this kernel reads: the workgroup kernel's)
         else bad = true;
       }
@@ -1868,6 +1880,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       if (ov_dis) atomicAdd(&st[26], (unsigned long long)ov_dis);
       if (ov_corr) atomicAdd(&st[27], (unsigned long long)ov_corr);
     }
+    if constexpr (METH != 0) { const bool any_multi = __any(multi); if (lane == 0 && any_multi) atomicAdd(meth_clipped_counter(P), 1u); }
   };
   if (!pmask) { flush_stats(); return; }                                  // nothing but fragments: no MI to work from
   const bool is_r1 = paired && (flags & bam::F_FIRST), is_r2 = paired && (flags & bam::F_LAST);
@@ -1977,8 +1990,9 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     const bool by_rank = CAP != 0 && capped[k];                    // a capped set's reads enter a column in (rank, file order): cap_ord
     // Methylation-aware mode (annotate_and_normalize, vanilla_caller.rs:781-860; methylation.rs:193-242): the call's anchor is the LAST longest
     // source read of the set (max_by_key; file order = lane order), taken over all its reads — a cap that bites is deferred above.  Every read here
-    // is one aligned block, so column p lies at the anchor's pos + p (forward) or at its last aligned base - p (reverse: the columns run in read
-    // orientation).  The strand of the call is is_top_strand of the anchor's flags (methylation.rs:392-398): C / T against a reference C, else G / A
+    // is one aligned block, alone or between clips — to the reference ONE M op of T bases, T = the lengths of all its ops, hard clips included —, so column
+    // p lies at the anchor's pos + p (forward) or at pos + T - 1 - p (reverse: the columns run in read orientation; with trailing clips that is NOT the
+    // last aligned base).  The strand of the call is is_top_strand of the anchor's flags (methylation.rs:392-398): C / T against a reference C, else G / A
     // against a reference G.  No annotation (no tags from this call, nothing normalised) when the anchor names no contig of the genome handed over.
     bool ann = false, a_rev = false;
     long long a_ref0 = 0;
@@ -1987,13 +2001,13 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     if constexpr (METH != 0) {
       const unsigned long long lm = members & __ballot(final_len == elen[k]);
       const uint32_t an = 63u - (uint32_t)__clzll((long long)lm);
-      const uint32_t a_flags = rlane(flags, an), a_lseq = rlane(l_seq, an);
+      const uint32_t a_flags = rlane(flags, an), a_tot = rlane(tot_len, an);   // (T: l_seq of a read of one op; more with hard clips)
       const int32_t a_pos = (int32_t)rlane((uint32_t)pos, an), a_ref = (int32_t)rlane((uint32_t)ref_id, an);
       a_rev = (a_flags & bam::F_REVERSE) != 0;
       const bool a_top = a_rev == ((a_flags & bam::F_LAST) != 0);
       tcode = a_top ? 2u : 4u; vcode = a_top ? 8u : 1u; target = a_top ? (uint32_t)'C' : (uint32_t)'G';
       ann = a_ref >= 0 && a_pos >= 0 && (uint32_t)a_ref < P.n_ref;
-      a_ref0 = a_rev ? (long long)a_pos + (long long)a_lseq - 1 : (long long)a_pos;
+      a_ref0 = a_rev ? (long long)a_pos + (long long)a_tot - 1 : (long long)a_pos;
       if (ann) { g_off = uniform_u64(P.contig_off[a_ref]); g_len = uniform_u64(P.contig_len[a_ref]); }
       ann_set[k] = ann;
     }
@@ -4163,6 +4177,7 @@ enum MiscWord : uint32_t {
   MISC_STATS = 0,            // [0, FGX_STATS_LEN): the caller's counters, k_reduce_stats's sums over the slots; [1] = consensus reads written
   MISC_COLS_USED = 28,
   MISC_N_DEFERRED = 29,      // families on the deferred list
+  MISC_N_METH_CLIPPED = 30,  // methylation-aware mode: decided families / molecules with a record of more than one CIGAR op (meth_clipped_counter)
   MISC_N_RETRY = 31,         // the retry list of the launch under way
   MISC_N_RETRY_OLD = 32,     // k_simplex_wave2 → k_family_wave<0>
   MISC_N_ROUTE = 33,         // k_split_cols → k_simplex_wave2
@@ -4178,6 +4193,7 @@ enum MiscWord : uint32_t {
 constexpr uint32_t MISC_SPLIT_WINDOW = MISC_N_BIG - MISC_N_RETRY + 1;   // retry, route and big counts of a split stage come back as ONE copy
 static_assert(FGX_STATS_LEN <= MISC_COLS_USED && MISC_BUILD_FAMILIES == 40 && MISC_BUILD_FAMILIES + (32 - FGX_STATS_LEN) <= MISC_N_SLOW,
               "k_reduce_stats writes words [0, FGX_STATS_LEN) and 40 .. of misc");
+static_assert(MISC_N_METH_CLIPPED == MISC_N_DEFERRED + 1 && MISC_N_METH_CLIPPED < MISC_READ_BACK, "meth_clipped_counter: the word behind the deferred count");
 static_assert(MISC_N_RETRY < MISC_N_ROUTE && MISC_N_ROUTE < MISC_N_BIG && MISC_SPLIT_WINDOW == 7 && MISC_N_SLOW < MISC_READ_BACK && MISC_READ_BACK <= MISC_WORDS, "misc layout");
 
 // ---- environment switches ---------------------------------------------------------------------------------------------------------------
@@ -4353,7 +4369,7 @@ struct Batch {
 
   // ---- buffers, counters, events ----
   void set_up() {
-    fp.last_meth_device = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
+    fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
     fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
@@ -4768,7 +4784,11 @@ struct Batch {
     DP.rows = fp.d_deep_rows.as<DeepRow>(); DP.fams = fp.d_deep_fams.as<DeepFam>(); DP.out_list = out; DP.n_out = cnt(MISC_N_DEEP);
     FastParams PD = P;
     PD.group_list = nullptr;
-    if (size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64>), dim3(n_list), dim3(64), 0, s, PD, DP);
+    // (methylation-aware mode: the clip-taking build of the record kernel, in every size class it runs)
+    if (meth_dev && size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64, 1>), dim3(n_list), dim3(64), 0, s, PD, DP);
+    else if (meth_dev && size_class == 2) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    else if (meth_dev && size_class == 3) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_CAP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    else if (size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64>), dim3(n_list), dim3(64), 0, s, PD, DP);
     else if (size_class == 1) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
     else if (size_class == 2) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
     else FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_CAP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
@@ -4991,6 +5011,7 @@ struct Batch {
     res->count = h_misc[MISC_STATS + 1];   // every consensus read of a fast-path family is one record
     for (int i = 0; i < FGX_STATS_LEN; i++) res->stats[i] = h_misc[MISC_STATS + i];
     res->n_deferred = (uint32_t)(h_misc[MISC_N_DEFERRED] & 0xFFFFFFFFull);
+    fp.last_meth_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] & 0xFFFFFFFFull);
     res->d_deferred = fp.d_deferred.as<uint32_t>();
     res->d_out_off = fp.d_offsets.as<uint64_t>();
     res->d_slot_size = fp.d_sizes.as<uint64_t>();

@@ -24,7 +24,8 @@
 //
 // Shape: k_simplex_wave2's record shape (simplex_wave2.inc), at most DEEP_MAX records (DEEP_CAP_MAX under --max-reads), at most 255
 // retained reads per end; no family with a fragment consensus AND a pair.  Everything else goes to k_family (up to 128 records) and
-// from there to the host path.
+// from there to the host path.  The methylation-aware mode's build of k_deep_parse (CLIPS 1, below) also takes reads with soft / hard clips around one
+// aligned block.
 //
 // --max-reads (downsample_filtered_source_reads, vanilla_caller.rs:902-932) is decided in k_deep_parse where the family gates are taken,
 // with the counters and in the order of k_family_wave<0> and k_family (fastpath.hip): per end, after the zero-length reads are out and
@@ -61,7 +62,8 @@ struct DeepFam {            // 64 bytes
   int32_t a_ref0[2];
   uint32_t a_info[2];       // contig | annotated << 28 | step is -1 << 29 | is_top_strand(anchor) << 30 | is_top_strand(first retained read) << 31
   uint32_t rej_down;        // retained reads that --max-reads dropped
-  uint32_t _pad[6];
+  uint32_t clipped;         // methylation-aware mode: a record of the family has more than one CIGAR op (k_deep_cols<1> counts the family once it is decided)
+  uint32_t _pad[5];
 };
 static_assert(sizeof(DeepRow) == 32 && sizeof(DeepFam) == 96, "deep descriptors");
 
@@ -106,13 +108,30 @@ struct DeepLds {
   uint32_t clen[3];
 };
 
+// What the clip-taking build of k_deep_parse keeps per record beside DeepLds: a read of the shape H* S* (M|=|X)+ S* H* is `lead` soft-clipped query
+// bases, an aligned block of `aln` bases at pos, and the rest of l_seq soft-clipped behind it; `tot` = the lengths of ALL its ops, hard clips included —
+// the one M op the reference's simplify_cigar_from_raw makes of it (S, H, =, X folded into M, neighbours merged)
+template <uint32_t MAXR>
+struct DeepClipLds : DeepLds<MAXR> {
+  uint16_t lead[MAXR], aln[MAXR], tot[MAXR];
+  uint32_t multi;                        // a record of the family has more than one CIGAR op
+};
+template <uint32_t MAXR, int CLIPS> struct DeepLdsOf { typedef DeepLds<MAXR> type; };
+template <uint32_t MAXR> struct DeepLdsOf<MAXR, 1> { typedef DeepClipLds<MAXR> type; };
+
 // <NT, MAXR>: threads per workgroup and the records a family may have — <128, 128> and <256, 512> for the families above 64 records, <256, 1024>
 // for those of more than 512 under --max-reads (an end fits its 255 reads after the cut only), <64, 64> for everything else when the streaming
 // kernels are the whole pipeline (methylation-aware mode: a wavefront per family, 3 KB of LDS)
-template <uint32_t NT, uint32_t MAXR>
+//
+// CLIPS 1: the build of the methylation-aware mode, which takes soft- / hard-clipped reads (H* S* (M|=|X)+ S* H*, up to WG_CIG_OPS ops) beside the
+// single-op ones.  The reference calls such a read in query space like any other (create_source_read :1094-1163 keeps the soft-clipped bases), so the
+// column kernel sees no difference; what the clips change is restated here: the mate clip (bam::mate_clip on the ops), the shared span of a pair (the
+// ALIGNED blocks overlap; the leading clip goes into the query offsets) and where the anchor's columns lie on the reference (step 6).  An indel read
+// still sends the family to the deferred list: its columns are not one run of reference positions.  CLIPS 0 is the kernel without any of it.
+template <uint32_t NT, uint32_t MAXR, int CLIPS = 0>
 __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
   constexpr uint32_t DEEP_NT = NT;
-  __shared__ DeepLds<MAXR> S;
+  __shared__ typename DeepLdsOf<MAXR, CLIPS>::type S;
   __shared__ __align__(16) uint8_t sTagCls[256];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t li = blockIdx.x;
@@ -122,6 +141,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
   fill_tag_classes(sTagCls);
   if (tid == 0) {
     S.bad = 0; S.rxbad = 0; S.ov_agree = S.ov_dis = S.ov_corr = 0;
+    if constexpr (CLIPS != 0) S.multi = 0;
     for (int e = 0; e < 3; e++) { S.cnt[e] = S.rem[e] = 0; S.fmin[e] = 0xFFFFFFFFu; S.fmax[e] = 0; S.rxcnt[e] = 0; S.rxfirst[e] = 0xFFFFFFFFu; S.clen[e] = 0; }
   }
   // not this path's: k_family decides (and defers what no device kernel takes)
@@ -155,6 +175,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
     uint32_t rx_rel = 0, rx_len = 0, cb_rel = 0, cb_len = 0;
     bool has_mi = false, has_rx = false, has_cb = false;
     uint32_t mi_len = 0;
+    uint32_t lead_s = 0, m_len = 0, tot_len = 0;   // (CLIPS) leading soft clip, aligned block, all ops
     if (len < 36u || len > 0xFFFFu || off > P.blob_len || (unsigned long long)len > P.blob_len - off) odd = true;
     else {
       const uint8_t* const rec = P.blob + off;
@@ -167,7 +188,8 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
       const unsigned long long aux_off = qual_off + l_seq;
       // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>); the methylation-aware mode needs a position
       const bool unm = (flags & bam::F_UNMAPPED) != 0;
-      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u) || (unm && P.meth_mode)) odd = true;
+      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || (CLIPS != 0 ? (unm || n_cig == 0 || n_cig > WG_CIG_OPS) : n_cig != (unm ? 0u : 1u)) ||
+          (unm && P.meth_mode)) odd = true;
       else {
         name_len = l_name - 1;
         ref_id = unm ? unmapped_ref_key(r) : (int32_t)gld32(rec); pos = (int32_t)gld32(rec + 4);   // (no shared span with an unmapped member, phase 2)
@@ -177,7 +199,24 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
         if (!unm) {
           if (pos < 0 || pos >= (1 << 30)) odd = true;
           const uint32_t op = gld32(rec + 32 + l_name), t = op & 15;
-          if (!(t == 0 || t == 7 || t == 8) || (op >> 4) != l_seq) odd = true;
+          if (CLIPS == 0 || n_cig == 1) {
+            if (!(t == 0 || t == 7 || t == 8) || (op >> 4) != l_seq) odd = true;
+            m_len = tot_len = l_seq;
+          } else if constexpr (CLIPS != 0) {
+            // clips around one aligned block (k_family_wave's walk): 0 leading clips, 1 the block, 2 trailing clips; I D N P are not this path's
+            uint32_t phase = 0, trail_s = 0;
+            bool okc = true;
+            for (uint32_t i = 0; i < n_cig; i++) {
+              const uint32_t o = i == 0 ? op : gld32(rec + 32 + l_name + 4 * i), ty = o & 15, ln = o >> 4;
+              tot_len += ln;                                   // (at most 16 lengths below 2^28)
+              if (ty == 0 || ty == 7 || ty == 8) { if (phase == 2) okc = false; phase = 1; m_len += ln; }
+              else if (ty == 4) { if (phase == 0) lead_s += ln; else { phase = 2; trail_s += ln; } }
+              else if (ty == 5) { if (phase == 1) phase = 2; }
+              else okc = false;
+            }
+            if (!okc || m_len == 0 || tot_len > 65535u || (unsigned long long)lead_s + m_len + trail_s != l_seq) odd = true;
+            atomicOr(&S.multi, 1u);
+          }
         }
         AuxTags ax;
         aux_walk(rec, sTagCls, (uint32_t)aux_off, len - (uint32_t)aux_off, P, ax);       // (offsets inside the record: below 2^16)
@@ -199,7 +238,20 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
             if (k == mc_len - 1 && ((v >> (8 * k)) & 0xFF) == 'M' && val > 0) { simple = true; ML = (int32_t)val; }
           }
           const int32_t mpos = (int32_t)gld32(rec + 24);
-          if (!simple || mpos < 0 || mpos >= (1 << 30)) odd = true;
+          if (CLIPS != 0 && !(simple && n_cig == 1 && mpos >= 0 && mpos < (1 << 30))) {
+            // the general rule on the ops.  Every function of it (bamrec.h: reference length, leading / trailing soft clip, query length, query bases
+            // up to a reference position, is_fr_pair) gives the same for H* S* (M|=|X)+ S* H* as for `lead S, block M, trail S`: hard clips count
+            // nowhere, soft clips are summed from either end, neighbouring aligned ops are walked as one — so three ops stand for the sixteen
+            uint32_t ops3[3] = {(lead_s << 4) | 4u, m_len << 4, ((l_seq - lead_s - m_len) << 4) | 4u};
+            uint32_t mops[MAX_MC_OPS];
+            bool overflow = false;
+            if (!odd) {
+              const bam::Rec v{rec, len};
+              const unsigned long long cl = bam::mate_clip(v, ops3, 3, rec + mc_lo, mc_len, mops, MAX_MC_OPS, &overflow);
+              if (overflow) odd = true;                        // (a mate of more ops than this kernel parses: the general path's)
+              clip = (uint32_t)(cl > 65535ull ? 65535ull : cl);
+            }
+          } else if (!simple || mpos < 0 || mpos >= (1 << 30)) odd = true;
           else {
             int32_t cl = 0;
             const int32_t mref = (int32_t)gld32(rec + 20);
@@ -252,6 +304,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
     S.off[r] = off; S.key[r] = (hash << 2) | pt; S.pos[r] = pos; S.ref_id[r] = ref_id;
     S.l_seq[r] = (uint16_t)l_seq; S.seq_rel[r] = (uint16_t)seq_rel; S.name_len[r] = (uint16_t)name_len; S.clip[r] = (uint16_t)clip; S.final_len[r] = 0;
     S.wo[r] = 0; S.mo[r] = 0; S.wc[r] = 0; S.partner[r] = -1;
+    if constexpr (CLIPS != 0) { S.lead[r] = (uint16_t)lead_s; S.aln[r] = (uint16_t)m_len; S.tot[r] = (uint16_t)tot_len; }
     S.rx_rel[r] = (uint16_t)rx_rel; S.cb_rel[r] = (uint16_t)cb_rel; S.rx_len[r] = (uint8_t)rx_len; S.cb_len[r] = (uint8_t)cb_len;
     S.bits[r] = (uint8_t)(ty | ((flags & bam::F_REVERSE) ? 4u : 0u) | (has_rx ? 8u : 0u) | (has_cb ? 16u : 0u) | ((flags & bam::F_LAST) ? 32u : 0u) |
                          ((flags & bam::F_UNMAPPED) ? 64u : 0u));
@@ -294,10 +347,17 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
       if (clater >= 0) continue;                            // a later R1 carries the name: this one is not paired
       const uint32_t b = (uint32_t)cmate;
       if (S.ref_id[a] != S.ref_id[b]) continue;
-      const int32_t s1 = S.pos[a] + 1, e1 = S.pos[a] + (int32_t)S.l_seq[a], s2 = S.pos[b] + 1, e2 = S.pos[b] + (int32_t)S.l_seq[b];
+      // (CLIPS: the aligned blocks share reference positions; a leading clip shifts the block's query offset — k_family_wave<0>'s restatement.  The CLIPS 0
+      // build has no aln / lead / tot arrays: it reads l_seq, here and at the anchor, in statements of its own)
+      int32_t s1, e1, s2, e2;
+      uint32_t qa = 0, qb = 0;
+      if constexpr (CLIPS != 0) {
+        s1 = S.pos[a] + 1; e1 = S.pos[a] + (int32_t)S.aln[a]; s2 = S.pos[b] + 1; e2 = S.pos[b] + (int32_t)S.aln[b];
+        qa = S.lead[a]; qb = S.lead[b];
+      } else { s1 = S.pos[a] + 1; e1 = S.pos[a] + (int32_t)S.l_seq[a]; s2 = S.pos[b] + 1; e2 = S.pos[b] + (int32_t)S.l_seq[b]; }
       const int32_t lox = s1 > s2 ? s1 : s2, hix = e1 < e2 ? e1 : e2;
       if (hix < lox) continue;
-      const uint32_t cnt = (uint32_t)(hix - lox + 1), o1 = (uint32_t)(lox - s1), o2 = (uint32_t)(lox - s2);
+      const uint32_t cnt = (uint32_t)(hix - lox + 1), o1 = (uint32_t)(lox - s1) + qa, o2 = (uint32_t)(lox - s2) + qb;
       S.wo[a] = (uint16_t)o1; S.mo[a] = (uint16_t)o2; S.wc[a] = (uint16_t)cnt; S.partner[a] = (int16_t)b;
       S.wo[b] = (uint16_t)o2; S.mo[b] = (uint16_t)o1; S.wc[b] = (uint16_t)cnt; S.partner[b] = (int16_t)a;
     }
@@ -487,6 +547,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
     f.rx_len_b = (uint8_t)((ne == 2u && S.rxcnt[2]) ? S.rx_len[S.rxfirst[2]] : 0u);
     f.rej_insuf = rej_insuf; f.rej_zero = rej_zero; f.rej_orphan = rej_orphan; f.rej_down = rej_down;
     f.ov_agree = S.ov_agree; f.ov_dis = S.ov_dis; f.ov_corr = S.ov_corr;
+    if constexpr (CLIPS != 0) f.clipped = S.multi;
     if (P.meth_mode && P.genome) {
       auto top_of = [&](uint32_t r) { return ((S.bits[r] & 4u) != 0) == ((S.bits[r] & 32u) != 0); };   // is_top_strand (methylation.rs:392-398): reverse == LAST
       for (uint32_t k = 0; k < ne; k++) {
@@ -501,7 +562,11 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
         const uint32_t ua = (uint32_t)a;
         const bool rv = (S.bits[ua] & 4u) != 0;
         const bool placed = S.ref_id[ua] >= 0 && S.pos[ua] >= 0 && (uint32_t)S.ref_id[ua] < P.n_ref;
-        f.a_ref0[k] = rv ? S.pos[ua] + (int32_t)S.l_seq[ua] - 1 : S.pos[ua];       // (one M op spanning the read: its reference span is l_seq)
+        // query_to_ref_positions (methylation.rs:116-184) on the ONE M op the reference makes of the read: a forward anchor's column p lies at pos + p —
+        // a leading clip shifts the lookup, as it does there —, a reverse anchor's at pos + T - 1 - p, T = the lengths of all its ops (l_seq when it
+        // is one op; with hard clips more than l_seq)
+        if constexpr (CLIPS != 0) f.a_ref0[k] = rv ? S.pos[ua] + (int32_t)S.tot[ua] - 1 : S.pos[ua];
+        else f.a_ref0[k] = rv ? S.pos[ua] + (int32_t)S.l_seq[ua] - 1 : S.pos[ua];
         f.a_info[k] = (placed ? ((uint32_t)S.ref_id[ua] & 0x0FFFFFFFu) | (1u << 28) : 0u) | (rv ? 1u << 29 : 0u) | (top_of(ua) ? 1u << 30 : 0u) | (top_of((uint32_t)first) ? 1u << 31 : 0u);
       }
     }
@@ -852,6 +917,7 @@ __global__ __launch_bounds__(256, FGX_DEEP_OCC) void k_deep_cols(FastParams P, D
     if (ov_agree) atomicAdd(&st[25], (unsigned long long)ov_agree);
     if (ov_dis) atomicAdd(&st[26], (unsigned long long)ov_dis);
     if (ov_corr) atomicAdd(&st[27], (unsigned long long)ov_corr);
+    if constexpr (METH != 0) { if (Fp->clipped) atomicAdd(meth_clipped_counter(P), 1u); }
   }
 }
 
