@@ -20,14 +20,16 @@
 
 namespace fgx {
 // canon_device.hip
-uint32_t launch_canon_molecules(hipStream_t s, bool codec, const canon::Params& P, const canon::CodecParams& PC, const uint8_t* d_blob,
+using canon::CANON_KIND_DUPLEX; using canon::CANON_KIND_CODEC; using canon::CANON_KIND_SIMPLEX;
+uint32_t launch_canon_molecules(hipStream_t s, int kind, const canon::Params& P, const canon::CodecParams& PC, const uint8_t* d_blob,
                                 const uint64_t* d_rec_off, const uint32_t* d_rec_len, const uint32_t* d_grp_first, const uint32_t* d_def, uint32_t nd,
                                 const uint64_t* d_first, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int* d_status,
-                                canon::Delta* d_delta, DevBuf& slabs);
+                                canon::Delta* d_delta, DevBuf& slabs, canon::RefRuns* d_runs, const rej::Params* PS);
 void canon_layout_device(hipStream_t s, const uint32_t* d_rec_len, const uint32_t* d_grp_first, const uint32_t* d_def, uint32_t nd, unsigned long long* work,
                          unsigned long long* d_first, DevBuf& out_off, DevBuf& scan_tmp, uint64_t* n_slots, uint64_t* bytes);
 void canon_compact_device(hipStream_t s, const int* d_status, const unsigned long long* d_first, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t nd,
-                          unsigned long long* work, DevBuf& c_off, DevBuf& c_len, DevBuf& c_grp, DevBuf& c_def, DevBuf& scan_tmp, uint32_t* n_cg, uint32_t* n_cr);
+                          unsigned long long* work, DevBuf& c_off, DevBuf& c_len, DevBuf& c_grp, DevBuf& c_def, DevBuf& scan_tmp, uint32_t* n_cg, uint32_t* n_cr,
+                          const canon::RefRuns* d_runs, DevBuf* c_runs);
 void resident_merge_device(hipStream_t s, uint32_t n_grp, const uint64_t* off1, const uint8_t* out1, uint64_t len1, const uint32_t* d_def, uint32_t nd, const uint32_t* c_def,
                            uint32_t n_cg, const uint64_t* off2, const uint8_t* out2, uint64_t len2, const uint32_t* again_list, uint32_t n_again, DevBuf& aux, DevBuf& scan_tmp,
                            uint8_t* d_used, DevBuf& final_out, uint64_t* final_len);
@@ -313,7 +315,7 @@ void fgx_destroy(fgx_caller* c) {
   (void)hipSetDevice(c->device);
   for (DevBuf* b : {&c->d_tables, &c->d_umi_tables, &c->d_stage, &c->d_reads, &c->d_jobs, &c->d_tiles, &c->d_ob, &c->d_oq, &c->d_od,
                     &c->d_oe, &c->d_scratch_a, &c->d_scratch_b, &c->d_in_blob, &c->d_in_off, &c->d_in_len, &c->d_in_grp, &c->d_mjobs, &c->d_mruns,
-                    &c->d_mtiles, &c->d_mflag, &c->d_mu, &c->d_mt, &c->d_canon_blob, &c->d_canon_off, &c->d_canon_len, &c->d_canon_grp, &c->d_canon_aux, &c->d_canon_slabs,
+                    &c->d_mtiles, &c->d_mflag, &c->d_mu, &c->d_mt, &c->d_canon_blob, &c->d_canon_off, &c->d_canon_len, &c->d_canon_grp, &c->d_canon_aux, &c->d_canon_slabs, &c->d_canon_runs, &c->d_canon_cruns,
                     &c->d_res_out1, &c->d_res_off1, &c->d_res_final, &c->d_res_aux, &c->d_res_aux2, &c->d_res_deferred, &c->d_res_scan, &c->d_res_cdef, &c->d_res_outoff})
     b->free_();
   c->genome.reset();
@@ -423,6 +425,20 @@ int fgx_canon_duplex_host(const fgx_options* o, const uint8_t* blob, const uint6
   delta5[0] = D.minority; for (int i = 0; i < 4; i++) delta5[1 + i] = D.ov[i];
   return rc;
 }
+// The same, with the reference runs of the methylation-aware mode: runs[i] (FGX_CANON_RUNS_WORDS dwords) = canon::RefRuns of surviving record i.
+int fgx_canon_duplex_runs_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
+                               uint64_t* delta5, uint32_t* runs) {
+  static_assert(sizeof(canon::RefRuns) == 4 * FGX_CANON_RUNS_WORDS, "fgumi_amd.h: FGX_CANON_RUNS_WORDS");
+  if (!o || o->struct_size != sizeof(fgx_options) || !blob || !out || !out_len || !delta5 || !runs) return 2;
+  static thread_local canon::Scratch S;
+  canon::Delta D;
+  std::vector<canon::RefRuns> rr(n ? n : 1);
+  memset(rr.data(), 0, rr.size() * sizeof(canon::RefRuns));
+  const int rc = canon::canon_duplex_molecule(canon_params(o), blob, rec_off, rec_len, n, out, rec_off, out_len, S, D, rr.data());
+  delta5[0] = D.minority; for (int i = 0; i < 4; i++) delta5[1 + i] = D.ov[i];
+  memcpy(runs, rr.data(), (size_t)n * sizeof(canon::RefRuns));
+  return rc;
+}
 
 static canon::CodecParams canon_codec_params(const fgx_options* o) {
   canon::CodecParams P;
@@ -444,6 +460,21 @@ static rej::Params reject_params(const fgx_options* o) {
   P.min_bq = o->min_input_base_quality; P.overlapping = o->overlapping_consensus; P.trim = o->trim; P.has_max_reads = o->max_reads >= 0;
   P.min_reads = o->min_reads; P.max_reads = o->max_reads < 0 ? 0u : o->max_reads > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)o->max_reads;
   return P;
+}
+// reject_core.h `canon_simplex_family` on the host: the canonical form of ONE simplex family (same contract as fgx_canon_duplex_host); `runs` may be NULL,
+// else it receives canon::RefRuns of every surviving record (FGX_CANON_RUNS_WORDS dwords each).  0, 1 = out of scope, 2 = bad arguments.
+int fgx_canon_simplex_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
+                           uint64_t* delta5, uint32_t* runs) {
+  if (!o || o->struct_size != sizeof(fgx_options) || !blob || !out || !out_len || !delta5) return 2;
+  static thread_local std::unique_ptr<rej::Scratch> S;
+  if (!S) S.reset(new rej::Scratch());
+  canon::Delta D;
+  std::vector<canon::RefRuns> rr(n ? n : 1);
+  memset(rr.data(), 0, rr.size() * sizeof(canon::RefRuns));
+  const int rc = canon::canon_simplex_family(reject_params(o), blob, rec_off, rec_len, n, out, rec_off, out_len, *S, D, rr.data());
+  delta5[0] = D.minority; for (int i = 0; i < 4; i++) delta5[1 + i] = D.ov[i];
+  if (runs) memcpy(runs, rr.data(), (size_t)n * sizeof(canon::RefRuns));
+  return rc;
 }
 // reject_core.h on the host: the `--rejects` stream of the simplex caller for a whole batch, computed from the records alone (mask pass
 // per group, then the rejected records — overlap-corrected copies, or the original bytes for a group below --min-reads — each with its
@@ -698,6 +729,22 @@ static bool duplex_canon_enabled() { return opt_in("FGX_DUPLEX_CANON"); }
 // a lane per molecule) from the records already uploaded, instead of on the host's cores; the records do not come back.
 static bool canon_device_enabled() { return opt_in("FGX_CANON_DEVICE"); }
 static bool codec_canon_enabled() { return opt_in("FGX_CODEC_CANON"); }
+// FGX_METH_CANON=1 (default off; it does not follow FGX_OPT_IN_ALL): the canonical second pass ALSO in the methylation-aware mode, for the duplex caller and — in
+// the mode only — for the simplex caller (reject_core.h canon_simplex_family).  The mode's annotation is tied to the anchor read's place on the reference, which the
+// canonical record no longer shows; so the pass emits every surviving record's reference runs (canon_core.h RefRuns: query_to_ref_positions on the ORIGINAL record)
+// and k_family_wave<1, 1> / k_deep_cols<1> look a column's reference base up through the anchor's runs.  Without the switch what the first pass defers in the mode
+// is the general path's, as before; with the mode off the simplex caller's routing does not change (k_family keeps its indel families).
+static bool meth_canon_enabled() { const char* e = getenv("FGX_METH_CANON"); return e && e[0] && e[0] != '0'; }
+// does the canonical second pass run for this caller?
+static bool canon_pass_enabled(const fgx_caller* c) {
+  const int kind = c->opt.caller_kind;
+  if (c->opt.methylation_mode != FGX_METHYLATION_DISABLED)
+    return meth_canon_enabled() && ((kind == FGX_CALLER_DUPLEX && duplex_canon_enabled()) || kind == FGX_CALLER_SIMPLEX);
+  return (kind == FGX_CALLER_DUPLEX && duplex_canon_enabled()) || (kind == FGX_CALLER_CODEC && codec_canon_enabled());
+}
+static int canon_kind(const fgx_caller* c) { return c->opt.caller_kind == FGX_CALLER_CODEC ? CANON_KIND_CODEC : c->opt.caller_kind == FGX_CALLER_SIMPLEX ? CANON_KIND_SIMPLEX : CANON_KIND_DUPLEX; }
+// the runs table of the canonical batch, for the one FastPath::run that decides it
+struct RefRunsScope { FastPath& fp; RefRunsScope(FastPath& f, const void* runs) : fp(f) { fp.ref_runs = runs; } ~RefRunsScope() { fp.ref_runs = nullptr; } };
 
 struct CanonPass {
   std::vector<uint8_t> used;            // per deferred group: 1 = its records come from the second device pass
@@ -727,15 +774,19 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
   std::vector<canon::Delta> delta(nd);
   memset(delta.data(), 0, nd * sizeof(canon::Delta));
   const bool codec = c->opt.caller_kind == FGX_CALLER_CODEC;
+  const int kind = canon_kind(c);
+  const rej::Params PS = reject_params(&c->opt);
+  const bool with_runs = c->opt.methylation_mode != FGX_METHYLATION_DISABLED;   // (FGX_METH_CANON=1: the records' reference runs travel with them)
+  std::vector<canon::RefRuns> runs(with_runs ? n_slots : 0);
   const canon::Params P = canon_params(&c->opt);
   const canon::CodecParams PC = canon_codec_params(&c->opt);
   c->d_canon_blob.reserve(bytes + 16);
   if (on_device) {
     // FGX_CANON_DEVICE=1: a lane per molecule over the records hybrid_upload already put on the device (canon_device.hip); the
     // canonical records are written into d_canon_blob there, and only status / lengths / delta come back
-    DevBuf& aux = c->d_canon_aux;      // first[nd+1] u64 | out_off[n_slots] u64 | delta[nd] | def[nd] u32 | status[nd] i32 | out_len[n_slots] u32
-    const size_t o_first = 0, o_off = o_first + (nd + 1) * 8, o_delta = o_off + n_slots * 8, o_def = o_delta + nd * sizeof(canon::Delta),
-                 o_status = o_def + nd * 4, o_len = o_status + nd * 4, total = o_len + n_slots * 4;
+    DevBuf& aux = c->d_canon_aux;      // first[nd+1] u64 | out_off[n_slots] u64 | delta[nd] | runs[n_slots] (the mode) | def[nd] u32 | status[nd] i32 | out_len[n_slots] u32
+    const size_t o_first = 0, o_off = o_first + (nd + 1) * 8, o_delta = o_off + n_slots * 8, o_runs = o_delta + nd * sizeof(canon::Delta),
+                 o_def = o_runs + runs.size() * sizeof(canon::RefRuns), o_status = o_def + nd * 4, o_len = o_status + nd * 4, total = o_len + n_slots * 4;
     aux.reserve(total + 16);
     uint8_t* a = aux.as<uint8_t>();
     hipStream_t s = c->stream;
@@ -744,9 +795,10 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
     hip_check(hipMemcpyAsync(a + o_first, first.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s), "H2D canonical slots");
     hip_check(hipMemcpyAsync(a + o_off, out_off.data(), n_slots * 8, hipMemcpyHostToDevice, s), "H2D canonical slot offsets");
     hip_check(hipMemcpyAsync(a + o_def, def.data(), nd * 4, hipMemcpyHostToDevice, s), "H2D deferred groups");
-    launch_canon_molecules(s, codec, P, PC, c->d_in_blob.as<uint8_t>(), c->d_in_off.as<uint64_t>(), c->d_in_len.as<uint32_t>(), c->d_in_grp.as<uint32_t>(),
+    launch_canon_molecules(s, kind, P, PC, c->d_in_blob.as<uint8_t>(), c->d_in_off.as<uint64_t>(), c->d_in_len.as<uint32_t>(), c->d_in_grp.as<uint32_t>(),
                            (const uint32_t*)(a + o_def), (uint32_t)nd, (const uint64_t*)(a + o_first), c->d_canon_blob.as<uint8_t>(), (const uint64_t*)(a + o_off),
-                           (uint32_t*)(a + o_len), (int*)(a + o_status), (canon::Delta*)(a + o_delta), c->d_canon_slabs);
+                           (uint32_t*)(a + o_len), (int*)(a + o_status), (canon::Delta*)(a + o_delta), c->d_canon_slabs, with_runs ? (canon::RefRuns*)(a + o_runs) : nullptr, &PS);
+    if (with_runs && n_slots) hip_check(hipMemcpyAsync(runs.data(), a + o_runs, runs.size() * sizeof(canon::RefRuns), hipMemcpyDeviceToHost, s), "D2H reference runs");
     hip_check(hipMemcpyAsync(status.data(), a + o_status, nd * 4, hipMemcpyDeviceToHost, s), "D2H canonical status");
     hip_check(hipMemcpyAsync(out_len.data(), a + o_len, n_slots * 4, hipMemcpyDeviceToHost, s), "D2H canonical lengths");
     if (!codec) hip_check(hipMemcpyAsync(delta.data(), a + o_delta, nd * sizeof(canon::Delta), hipMemcpyDeviceToHost, s), "D2H canonical delta");
@@ -755,12 +807,19 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
     unsigned T = host_threads();
     if (T > nd / 64 + 1) T = (unsigned)(nd / 64 + 1);
     auto work = [&](unsigned t) {
-      std::unique_ptr<canon::Scratch> S(codec ? nullptr : new canon::Scratch());
+      std::unique_ptr<canon::Scratch> S(kind == CANON_KIND_DUPLEX ? new canon::Scratch() : nullptr);
       std::unique_ptr<canon::CodecScratch> SC(codec ? new canon::CodecScratch() : nullptr);
+      std::unique_ptr<rej::Scratch> SS(kind == CANON_KIND_SIMPLEX ? new rej::Scratch() : nullptr);
       for (size_t k = t; k < nd; k += T) {
         const uint32_t r0 = grp_first[def[k]], n = grp_first[def[k] + 1] - r0;
+        if (kind == CANON_KIND_SIMPLEX) {
+          status[k] = canon::canon_simplex_family(PS, records, rec_off + r0, rec_len + r0, n, blob.data(), out_off.data() + first[k], out_len.data() + first[k], *SS, delta[k],
+                                                  with_runs ? runs.data() + first[k] : nullptr);
+          continue;
+        }
         status[k] = codec ? canon::canon_codec_molecule(PC, records, rec_off + r0, rec_len + r0, n, blob.data(), out_off.data() + first[k], out_len.data() + first[k], *SC)
-                          : canon::canon_duplex_molecule(P, records, rec_off + r0, rec_len + r0, n, blob.data(), out_off.data() + first[k], out_len.data() + first[k], *S, delta[k]);
+                          : canon::canon_duplex_molecule(P, records, rec_off + r0, rec_len + r0, n, blob.data(), out_off.data() + first[k], out_len.data() + first[k], *S, delta[k],
+                                                          with_runs ? runs.data() + first[k] : nullptr);
       }
     };
     if (T <= 1) work(0);
@@ -769,11 +828,13 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
   // the canonical molecules as one batch
   std::vector<uint64_t> c_off;
   std::vector<uint32_t> c_len, c_grp(1, 0), c_def;
+  std::vector<canon::RefRuns> c_runs;
   for (size_t k = 0; k < nd; k++) {
     if (status[k] != canon::CANON_OK) continue;
     for (uint64_t i = first[k]; i < first[k + 1]; i++)
       if (out_len[i]) {
         c_off.push_back(out_off[i]); c_len.push_back(out_len[i]);
+        if (with_runs) c_runs.push_back(runs[i]);
         if (!on_device) { const uint32_t L = out_len[i]; memcpy(blob.data() + out_off[i] - 4, &L, 4); }   // (the kernel wrote its own prefixes)
       }
     c_grp.push_back((uint32_t)c_off.size());
@@ -787,11 +848,18 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
   if (n_cr) {
     hip_check(hipMemcpyAsync(c->d_canon_off.p, c_off.data(), (size_t)n_cr * 8, hipMemcpyHostToDevice, c->stream), "H2D canonical rec_off");
     hip_check(hipMemcpyAsync(c->d_canon_len.p, c_len.data(), (size_t)n_cr * 4, hipMemcpyHostToDevice, c->stream), "H2D canonical rec_len");
+    if (with_runs) {
+      c->d_canon_cruns.reserve((size_t)(n_cr + 1) * sizeof(canon::RefRuns));
+      hip_check(hipMemcpyAsync(c->d_canon_cruns.p, c_runs.data(), (size_t)n_cr * sizeof(canon::RefRuns), hipMemcpyHostToDevice, c->stream), "H2D reference runs");
+    }
   }
   hip_check(hipMemcpyAsync(c->d_canon_grp.p, c_grp.data(), (size_t)(n_cg + 1) * 4, hipMemcpyHostToDevice, c->stream), "H2D canonical grp_first");
   hip_check(hipStreamSynchronize(c->stream), "sync");
   FastResult fr2;
-  c->fast->fp.run(c, c->d_canon_blob.as<uint8_t>(), bytes, c->d_canon_off.as<uint64_t>(), c->d_canon_len.as<uint32_t>(), n_cr, c->d_canon_grp.as<uint32_t>(), n_cg, &fr2);
+  {
+    RefRunsScope rs(c->fast->fp, with_runs && n_cr ? c->d_canon_cruns.p : nullptr);
+    c->fast->fp.run(c, c->d_canon_blob.as<uint8_t>(), bytes, c->d_canon_off.as<uint64_t>(), c->d_canon_len.as<uint32_t>(), n_cr, c->d_canon_grp.as<uint32_t>(), n_cg, &fr2);
+  }
   cp.out.resize(fr2.out_len);
   if (fr2.out_len) hip_check(hipMemcpy(cp.out.data(), fr2.d_out, fr2.out_len, hipMemcpyDeviceToHost), "D2H canonical out");
   std::vector<uint64_t> slot2((size_t)3 * n_cg);
@@ -854,11 +922,9 @@ static int hybrid_after_upload(fgx_caller* c, general_fn general, const uint8_t*
   cp.used.assign(def.size(), 0);
   c->last_canon_molecules = 0;
   c->last_deferred_groups = (uint64_t)def.size();
-  // (not in the methylation-aware mode: the canonical form moves and re-lengths the reads, and an annotation is tied to its anchor's place on the reference —
-  // what the device pass defers there is the general path's)
-  if (c->opt.methylation_mode == FGX_METHYLATION_DISABLED &&
-      ((c->opt.caller_kind == FGX_CALLER_DUPLEX && duplex_canon_enabled()) || (c->opt.caller_kind == FGX_CALLER_CODEC && codec_canon_enabled())))
-    canon_second_pass(c, records, rec_off, rec_len, grp_first, def, cp);
+  // (in the methylation-aware mode only with FGX_METH_CANON=1: the canonical form moves and re-lengths the reads, and an annotation is tied to its anchor's place
+  // on the reference — the pass then hands the kernels the records' reference runs; without the switch what the device pass defers there is the general path's)
+  if (canon_pass_enabled(c)) canon_second_pass(c, records, rec_off, rec_len, grp_first, def, cp);
   std::vector<uint64_t> d_off;
   std::vector<uint32_t> d_len, d_grp(1, 0);
   for (size_t k = 0; k < def.size(); k++) {
@@ -943,10 +1009,7 @@ int fgx_process_batch(fgx_caller* c, const uint8_t* records, uint64_t records_le
 // pass, and the two passes' records are merged in group order on the device; what the canonical form cannot express, or the second pass
 // defers again, stays in the deferred list the caller re-submits.  The host sees the deferred indices, per-molecule status and counted
 // deltas — never a record.  Default since round 4 (FGX_CANON_RESIDENT=0 opts out); tests/test_apiemu.py also runs it on the CPU.
-static bool canon_resident_enabled(int kind) {
-  if (!opt_in("FGX_CANON_RESIDENT")) return false;
-  return (kind == FGX_CALLER_DUPLEX && duplex_canon_enabled()) || (kind == FGX_CALLER_CODEC && codec_canon_enabled());
-}
+static bool canon_resident_enabled(const fgx_caller* c) { return opt_in("FGX_CANON_RESIDENT") && canon_pass_enabled(c); }
 
 struct ResidentOut { const uint8_t* d_out; uint64_t out_len, count, stats[FGX_STATS_LEN]; uint32_t n_deferred; const uint32_t* d_deferred; uint64_t n_canon; double ms_kernels;
                      const uint64_t* d_group_off; };   // byte offset of every group in the merged stream (n_grp + 1 entries, device)
@@ -956,6 +1019,8 @@ static bool canon_resident_pass(fgx_caller* c, const uint8_t* d_blob, const uint
   hipStream_t s = c->stream;
   const uint32_t nd = fr.n_deferred;
   const bool codec = c->opt.caller_kind == FGX_CALLER_CODEC;
+  const rej::Params PS = reject_params(&c->opt);
+  const bool with_runs = c->opt.methylation_mode != FGX_METHYLATION_DISABLED;   // (FGX_METH_CANON=1: the records' reference runs travel with them)
   std::vector<uint32_t> def(nd);
   hip_check(hipMemcpy(def.data(), fr.d_deferred, (size_t)nd * 4, hipMemcpyDeviceToHost), "D2H deferred");
   std::sort(def.begin(), def.end());
@@ -987,15 +1052,20 @@ static bool canon_resident_pass(fgx_caller* c, const uint8_t* d_blob, const uint
   uint32_t* d_out_len = c->d_canon_aux.as<uint32_t>();
   hip_check(hipMemsetAsync(c->d_canon_blob.p, 0, bytes + 16, s), "memset canonical blob");
   hip_check(hipMemsetAsync(d_out_len, 0, n_slots * 4 + 4, s), "memset canonical lengths");
-  launch_canon_molecules(s, codec, canon_params(&c->opt), canon_codec_params(&c->opt), d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, (const uint64_t*)d_first,
-                         c->d_canon_blob.as<uint8_t>(), c->d_res_outoff.as<uint64_t>(), d_out_len, d_status, d_delta, c->d_canon_slabs);
+  if (with_runs) c->d_canon_runs.reserve((size_t)(n_slots + 1) * sizeof(canon::RefRuns));
+  canon::RefRuns* const d_runs = with_runs ? c->d_canon_runs.as<canon::RefRuns>() : nullptr;
+  launch_canon_molecules(s, canon_kind(c), canon_params(&c->opt), canon_codec_params(&c->opt), d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, (const uint64_t*)d_first,
+                         c->d_canon_blob.as<uint8_t>(), c->d_res_outoff.as<uint64_t>(), d_out_len, d_status, d_delta, c->d_canon_slabs, d_runs, &PS);
   uint32_t n_cg = 0, n_cr = 0;
   canon_compact_device(s, d_status, d_first, c->d_res_outoff.as<uint64_t>(), d_out_len, nd, work, c->d_canon_off, c->d_canon_len, c->d_canon_grp, c->d_res_cdef, c->d_res_scan,
-                       &n_cg, &n_cr);
+                       &n_cg, &n_cr, d_runs, &c->d_canon_cruns);
   hip_check(hipStreamSynchronize(s), "canonical lists");
   if (n_cg == 0) return false;                                   // nothing in scope: the first pass's buffers are untouched
   FastResult fr2;
-  c->fast->fp.run(c, c->d_canon_blob.as<uint8_t>(), bytes, c->d_canon_off.as<uint64_t>(), c->d_canon_len.as<uint32_t>(), n_cr, c->d_canon_grp.as<uint32_t>(), n_cg, &fr2);
+  {
+    RefRunsScope rs(c->fast->fp, with_runs && n_cr ? c->d_canon_cruns.p : nullptr);
+    c->fast->fp.run(c, c->d_canon_blob.as<uint8_t>(), bytes, c->d_canon_off.as<uint64_t>(), c->d_canon_len.as<uint32_t>(), n_cr, c->d_canon_grp.as<uint32_t>(), n_cg, &fr2);
+  }
   uint64_t final_len = 0;
   resident_merge_device(s, n_grp, c->d_res_off1.as<uint64_t>(), c->d_res_out1.as<uint8_t>(), len1, d_def, nd, c->d_res_cdef.as<uint32_t>(), n_cg, fr2.d_out_off, fr2.d_out,
                         fr2.out_len, fr2.d_deferred, fr2.n_deferred, c->d_res_aux2, c->d_res_scan, d_used, c->d_res_final, &final_len);
@@ -1055,7 +1125,7 @@ int fgx_process_batch_device(fgx_caller* c, const void* d_records, uint64_t reco
     c->last_deferred_groups = fr.n_deferred; c->last_canon_molecules = 0;
     c->last_group_off = fr.d_out_off; c->last_group_stride = 3;
     uint32_t left_deferred = fr.n_deferred;      // (after the canonical second pass, when it runs)
-    if (fr.n_deferred > 0 && c->opt.methylation_mode == FGX_METHYLATION_DISABLED && canon_resident_enabled(c->opt.caller_kind)) {   // (never in the methylation-aware mode: see hybrid_after_upload)
+    if (fr.n_deferred > 0 && canon_resident_enabled(c)) {   // (in the methylation-aware mode only with FGX_METH_CANON=1: see hybrid_after_upload)
       ResidentOut ro;
       if (canon_resident_pass(c, (const uint8_t*)d_records, (const uint64_t*)d_rec_off, (const uint32_t*)d_rec_len, (const uint32_t*)d_grp_first, n_grp, fr, &ro)) {
         c->fast->has_last = false;                  // (the slot tables of `last` describe one pass only: fgx_filter_last_output_device has to be given the records)

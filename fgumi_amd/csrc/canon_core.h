@@ -24,6 +24,9 @@
 // qualities), a per-strand cap that would bite, more than MAX_READS records / MAX_OPS CIGAR ops / MAX_GROUPS alignment groups,
 // fragments, secondary / supplementary / unmapped records, a strand-orientation collision, records the reference refuses.
 //
+// The simplex caller's canonical form (`canon_simplex_family`; used in the methylation-aware mode) is in reject_core.h, beside the restatement of the
+// simplex gates it is built from.
+//
 // Host + device source, scalar, no allocation: one GPU lane (or one host thread) per molecule.
 #pragma once
 #include <cstdint>
@@ -45,6 +48,8 @@ constexpr uint32_t MAX_GROUPS = 16;
 constexpr int32_t OTHER_REF_XOR = 0x20000000;   // R2 records of the canonical molecule: ref_id ^ this
 
 enum : int { CANON_OK = 0, CANON_OUT_OF_SCOPE = 1 };
+// which form a pass computes (launch_canon_molecules, canon_device.hip; 0 / 1 are what the `codec` boolean of that interface was); the simplex form is in reject_core.h
+enum : int { CANON_KIND_DUPLEX = 0, CANON_KIND_CODEC = 1, CANON_KIND_SIMPLEX = 2 };
 
 struct Params {
   uint8_t min_bq;                 // min_input_base_quality
@@ -78,6 +83,45 @@ struct Delta {
   uint64_t minority;             // reads dropped by the alignment filter (MinorityAlignment; also total_reads / filtered_reads)
   uint64_t ov[4];                // CorrectionStats of the overlap pre-step
 };
+
+// ---- reference runs (methylation-aware mode) -------------------------------------------------------------------------------------
+// The canonical record has lost its place on the reference (`<len>M` at the old pos, R2 on another reference id), and the mode's
+// annotation is tied to the anchor read's place: query_to_ref_positions (methylation.rs:116-178) walks the anchor's simplified,
+// reversed, truncated CIGAR from pos (forward) or from pos + span - 1 down (reverse; span over the folded ORIGINAL CIGAR, S H = X as M,
+// so clips count).  The canonical pass therefore emits, beside every surviving record, that walk's result on the ORIGINAL record as a
+// short list of aligned runs — methylation_core.h's MethRun in fixed-size form — which the methylation builds of the kernels read
+// instead of their one `pos + p` / `pos + T - 1 - p` run.  M ops of a simplified CIGAR are never adjacent: at most MAX_OPS / 2 runs.
+constexpr uint32_t MAX_RUNS = MAX_OPS / 2;
+struct RefRun { uint32_t q0, len; int64_t ref0; };   // columns [q0, q0 + len) lie at ref0, ref0 + step, ...; step = -1 for a reverse record
+struct RefRuns {
+  int32_t ref_id;        // the ORIGINAL reference id (rewrite_record moves R2 away); -1: no place on a reference (pos < 0)
+  uint32_t n_rev;        // number of runs | REVERSE bit << 31
+  RefRun run[MAX_RUNS];
+};
+static_assert(sizeof(RefRuns) == 8 + 16 * MAX_RUNS, "RefRuns: the kernels read it as dwords");
+
+// `simp` / `n_simp`: ReadInfo::simp of the record; `ops`: its raw CIGAR.
+CANON_HD void ref_runs_of(const SimpOp* simp, uint32_t n_simp, const uint32_t* ops, uint32_t nc, int32_t ref_id, int32_t pos, bool rev, RefRuns& out) {
+  out.ref_id = pos >= 0 ? ref_id : -1;
+  int64_t ref_pos = pos;
+  if (rev) {
+    int64_t span = 0;
+    for (uint32_t k = 0; k < nc; k++) { const uint32_t t = ops[k] & 0xF; if (t != 1 && t != 6 && t <= 8) span += ops[k] >> 4; }   // M D N S H = X
+    ref_pos = (int64_t)pos + span - 1;
+  }
+  const int64_t step = rev ? -1 : 1;
+  uint32_t n = 0, q = 0;
+  for (uint32_t k = 0; k < n_simp; k++) {
+    const uint32_t len = simp[k].len;
+    if (simp[k].k == 0) {
+      if (len > 0 && n < MAX_RUNS) { out.run[n].q0 = q; out.run[n].len = len; out.run[n].ref0 = ref_pos; n++; }
+      q += len; ref_pos += step * (int64_t)len;
+    } else if (simp[k].k == 1) q += len;                               // insertion: no reference base
+    else if (simp[k].k == 2 || simp[k].k == 3) ref_pos += step * (int64_t)len;   // deletion / skip
+  }
+  for (uint32_t k = n; k < MAX_RUNS; k++) { out.run[k].q0 = 0; out.run[k].len = 0; out.run[k].ref0 = 0; }
+  out.n_rev = n | (rev ? 0x80000000u : 0u);
+}
 
 CANON_HD void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 CANON_HD void wr16(uint8_t* p, uint16_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
@@ -288,8 +332,9 @@ CANON_HD uint32_t rewrite_record(uint8_t* rec, uint32_t n, uint32_t clip, bool m
 
 // One duplex molecule: records `n` at rec_off / rec_len in `blob` → canonical records in `out` at out_off[i] (room for rec_len[i]
 // bytes each), out_len[i] = new length, 0 = the record is dropped.  Returns CANON_OK or CANON_OUT_OF_SCOPE (outputs undefined).
+// `runs` (methylation-aware mode, else null): runs[i] = the reference runs of surviving record i.
 CANON_HD int canon_duplex_molecule(const Params& P, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out,
-                                   const uint64_t* out_off, uint32_t* out_len, Scratch& S, Delta& D) {
+                                   const uint64_t* out_off, uint32_t* out_len, Scratch& S, Delta& D, RefRuns* runs = nullptr) {
   D.minority = 0; D.ov[0] = D.ov[1] = D.ov[2] = D.ov[3] = 0;
   if (n == 0 || n > MAX_READS || P.trim) return CANON_OUT_OF_SCOPE;
   if (P.min_xy > P.min_total || P.min_yx > P.min_xy) return CANON_OUT_OF_SCOPE;          // the reference refuses the options
@@ -436,6 +481,12 @@ CANON_HD int canon_duplex_molecule(const Params& P, const uint8_t* blob, const u
   // the canonical records
   for (uint32_t i = 0; i < n; i++) {
     if (!S.r[i].keep) { out_len[i] = 0; continue; }
+    if (runs) {   // (methylation-aware mode) the record's place on the reference, from the header and CIGAR the rewrite is about to replace
+      bam::Rec v{out + out_off[i], rec_len[i]};
+      const uint32_t nc = v.n_cigar();
+      for (uint32_t k = 0; k < nc; k++) S.ops[k] = v.cigar_op(k);
+      ref_runs_of(S.r[i].simp, S.r[i].n_simp, S.ops, nc, v.ref_id(), v.pos(), (v.flags() & bam::F_REVERSE) != 0, runs[i]);
+    }
     out_len[i] = rewrite_record(out + out_off[i], rec_len[i], S.r[i].clip, S.r[i].r2 != 0);
   }
   return CANON_OK;

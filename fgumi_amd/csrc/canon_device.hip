@@ -14,6 +14,7 @@
 // in flight against 16 threads.  A grid-stride loop bounds the slabs (at most MAX_LANES of them).
 #include "engine.h"
 #include "canon_core.h"
+#include "reject_core.h"
 #ifndef FGX_DEVEMU            // (tests/devemu compiles this file for the host with a serial scan)
 #include <hipcub/hipcub.hpp>
 #endif
@@ -21,7 +22,8 @@
 namespace fgx {
 
 constexpr uint32_t CANON_BLOCK = 64;          // one wavefront per workgroup: divergent scalar code gains nothing from more
-constexpr uint32_t CANON_MAX_LANES = 32768;   // slabs: 32768 x 33 KB = 1.1 GB at most
+constexpr uint32_t CANON_MAX_LANES = 32768;   // slabs: 32768 x 33 KB = 1.1 GB at most (CODEC; duplex 19 KB, simplex — rej::Scratch — 22 KB a lane)
+using canon::CANON_KIND_DUPLEX; using canon::CANON_KIND_CODEC; using canon::CANON_KIND_SIMPLEX;
 
 // the 4-byte block_size ahead of every kept canonical record (the slot layout leaves room for it): the blob reads as a BAM record stream
 __device__ inline void write_prefixes(uint8_t* out, const uint64_t* out_off, const uint32_t* out_len, uint32_t n) {
@@ -31,13 +33,14 @@ __device__ inline void write_prefixes(uint8_t* out, const uint64_t* out_off, con
 __global__ void __launch_bounds__(CANON_BLOCK)
 k_canon_duplex(canon::Params P, const uint8_t* __restrict__ blob, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ rec_len,
                const uint32_t* __restrict__ grp_first, const uint32_t* __restrict__ def, uint32_t nd, const uint64_t* __restrict__ first,
-               uint8_t* out, const uint64_t* __restrict__ out_off, uint32_t* out_len, int* status, canon::Delta* delta, canon::Scratch* slabs) {
+               uint8_t* out, const uint64_t* __restrict__ out_off, uint32_t* out_len, int* status, canon::Delta* delta, canon::Scratch* slabs,
+               canon::RefRuns* runs) {                      // (methylation-aware mode, else null: the reference runs of every slot)
   const uint32_t lane = blockIdx.x * CANON_BLOCK + threadIdx.x, stride = gridDim.x * CANON_BLOCK;
   canon::Scratch& S = slabs[lane];
   for (uint32_t k = lane; k < nd; k += stride) {
     const uint32_t r0 = grp_first[def[k]], n = grp_first[def[k] + 1] - r0;
     canon::Delta D;
-    const int st = canon::canon_duplex_molecule(P, blob, rec_off + r0, rec_len + r0, n, out, out_off + first[k], out_len + first[k], S, D);
+    const int st = canon::canon_duplex_molecule(P, blob, rec_off + r0, rec_len + r0, n, out, out_off + first[k], out_len + first[k], S, D, runs ? runs + first[k] : nullptr);
     status[k] = st;
     delta[k] = D;
     if (st == canon::CANON_OK) write_prefixes(out, out_off + first[k], out_len + first[k], n);
@@ -58,24 +61,45 @@ k_canon_codec(canon::CodecParams P, const uint8_t* __restrict__ blob, const uint
   }
 }
 
+// simplex families (the methylation-aware mode with FGX_METH_CANON=1): reject_core.h canon_simplex_family, same contract
+__global__ void __launch_bounds__(CANON_BLOCK)
+k_canon_simplex(rej::Params P, const uint8_t* __restrict__ blob, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ rec_len,
+                const uint32_t* __restrict__ grp_first, const uint32_t* __restrict__ def, uint32_t nd, const uint64_t* __restrict__ first,
+                uint8_t* out, const uint64_t* __restrict__ out_off, uint32_t* out_len, int* status, canon::Delta* delta, rej::Scratch* slabs, canon::RefRuns* runs) {
+  const uint32_t lane = blockIdx.x * CANON_BLOCK + threadIdx.x, stride = gridDim.x * CANON_BLOCK;
+  rej::Scratch& S = slabs[lane];
+  for (uint32_t k = lane; k < nd; k += stride) {
+    const uint32_t r0 = grp_first[def[k]], n = grp_first[def[k] + 1] - r0;
+    canon::Delta D;
+    const int st = canon::canon_simplex_family(P, blob, rec_off + r0, rec_len + r0, n, out, out_off + first[k], out_len + first[k], S, D, runs ? runs + first[k] : nullptr);
+    status[k] = st;
+    delta[k] = D;
+    if (st == canon::CANON_OK) write_prefixes(out, out_off + first[k], out_len + first[k], n);
+  }
+}
+
 // Launches the canonicalisation of the `nd` deferred molecules def[0..nd) of the batch at d_blob / d_rec_off / d_rec_len / d_grp_first.
 // d_first[k] = first record slot of molecule k in d_out_off / d_out_len (the caller laid the slots out); results stay on the device.
-// `slabs` is grown as needed.  Returns the number of lanes launched.
-uint32_t launch_canon_molecules(hipStream_t s, bool codec, const canon::Params& P, const canon::CodecParams& PC, const uint8_t* d_blob,
+// `kind`: CANON_KIND_DUPLEX (0), CANON_KIND_CODEC (1) or CANON_KIND_SIMPLEX (2, with its parameters in `PS`).  `slabs` is grown as needed.  `d_runs` (duplex and simplex in the methylation-aware mode, else null): room for one canon::RefRuns per slot.  Returns the number of lanes launched.
+uint32_t launch_canon_molecules(hipStream_t s, int kind, const canon::Params& P, const canon::CodecParams& PC, const uint8_t* d_blob,
                                 const uint64_t* d_rec_off, const uint32_t* d_rec_len, const uint32_t* d_grp_first, const uint32_t* d_def, uint32_t nd,
                                 const uint64_t* d_first, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int* d_status,
-                                canon::Delta* d_delta, DevBuf& slabs) {
+                                canon::Delta* d_delta, DevBuf& slabs, canon::RefRuns* d_runs = nullptr, const rej::Params* PS = nullptr) {
   if (nd == 0) return 0;
+  const bool codec = kind == CANON_KIND_CODEC, simplex = kind == CANON_KIND_SIMPLEX;
   uint32_t blocks = (nd + CANON_BLOCK - 1) / CANON_BLOCK;
   if (blocks > CANON_MAX_LANES / CANON_BLOCK) blocks = CANON_MAX_LANES / CANON_BLOCK;
   const uint32_t lanes = blocks * CANON_BLOCK;
-  slabs.reserve((size_t)lanes * (codec ? sizeof(canon::CodecScratch) : sizeof(canon::Scratch)));
-  if (codec)
+  slabs.reserve((size_t)lanes * (codec ? sizeof(canon::CodecScratch) : simplex ? sizeof(rej::Scratch) : sizeof(canon::Scratch)));
+  if (simplex)
+    hipLaunchKernelGGL(k_canon_simplex, dim3(blocks), dim3(CANON_BLOCK), 0, s, *PS, d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, d_first, d_out, d_out_off,
+                       d_out_len, d_status, d_delta, slabs.as<rej::Scratch>(), d_runs);
+  else if (codec)
     hipLaunchKernelGGL(k_canon_codec, dim3(blocks), dim3(CANON_BLOCK), 0, s, PC, d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, d_first, d_out, d_out_off,
                        d_out_len, d_status, slabs.as<canon::CodecScratch>());
   else
     hipLaunchKernelGGL(k_canon_duplex, dim3(blocks), dim3(CANON_BLOCK), 0, s, P, d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, d_first, d_out, d_out_off,
-                       d_out_len, d_status, d_delta, slabs.as<canon::Scratch>());
+                       d_out_len, d_status, d_delta, slabs.as<canon::Scratch>(), d_runs);
   hip_check(hipGetLastError(), "k_canon launch");
   return lanes;
 }
@@ -121,7 +145,7 @@ __global__ void k_canon_kept(const int* __restrict__ status, const unsigned long
 // the canonical batch: rec_off / rec_len of the kept records, grp_first, and the deferred index of each canonical group
 __global__ void k_canon_lists(const int* __restrict__ status, const unsigned long long* __restrict__ first, const uint64_t* __restrict__ out_off,
                               const uint32_t* __restrict__ out_len, uint32_t nd, const unsigned long long* __restrict__ rbase, const unsigned long long* __restrict__ gidx,
-                              uint64_t* c_off, uint32_t* c_len, uint32_t* c_grp, uint32_t* c_def) {
+                              uint64_t* c_off, uint32_t* c_len, uint32_t* c_grp, uint32_t* c_def, const canon::RefRuns* __restrict__ runs, canon::RefRuns* c_runs) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= nd) return;
   if (k == nd - 1) c_grp[gidx[nd]] = (uint32_t)rbase[nd];                  // the closing boundary
@@ -129,7 +153,7 @@ __global__ void k_canon_lists(const int* __restrict__ status, const unsigned lon
   const unsigned long long g = gidx[k];
   c_grp[g] = (uint32_t)rbase[k]; c_def[g] = k;
   unsigned long long w = rbase[k];
-  for (unsigned long long i = first[k]; i < first[k + 1]; i++) if (out_len[i]) { c_off[w] = out_off[i]; c_len[w] = out_len[i]; w++; }
+  for (unsigned long long i = first[k]; i < first[k + 1]; i++) if (out_len[i]) { c_off[w] = out_off[i]; c_len[w] = out_len[i]; if (runs) c_runs[w] = runs[i]; w++; }
 }
 __global__ void k_res_again(const uint32_t* __restrict__ again_list, uint32_t n_again, uint8_t* again) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -195,9 +219,11 @@ void canon_layout_device(hipStream_t s, const uint32_t* d_rec_len, const uint32_
   hip_check(hipGetLastError(), "k_canon_fill launch");
 }
 
-// The canonical batch out of the kernel's results: c_off / c_len / c_grp / c_def (grown as needed).  `work` as above.
+// The canonical batch out of the kernel's results: c_off / c_len / c_grp / c_def (grown as needed).  `work` as above.  With `d_runs` (the per-slot
+// reference runs of the methylation-aware mode) `c_runs` gets the runs of the kept records, compacted by the same scan: entry w belongs to record w.
 void canon_compact_device(hipStream_t s, const int* d_status, const unsigned long long* d_first, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t nd,
-                          unsigned long long* work, DevBuf& c_off, DevBuf& c_len, DevBuf& c_grp, DevBuf& c_def, DevBuf& scan_tmp, uint32_t* n_cg, uint32_t* n_cr) {
+                          unsigned long long* work, DevBuf& c_off, DevBuf& c_len, DevBuf& c_grp, DevBuf& c_def, DevBuf& scan_tmp, uint32_t* n_cg, uint32_t* n_cr,
+                          const canon::RefRuns* d_runs = nullptr, DevBuf* c_runs = nullptr) {
   unsigned long long* kept = work; unsigned long long* ok = work + (nd + 1); unsigned long long* rbase = work + 2ull * (nd + 1); unsigned long long* gidx = work + 3ull * (nd + 1);
   hip_check(hipMemsetAsync(work, 0, 4ull * (nd + 1) * 8, s), "memset compaction");
   hipLaunchKernelGGL(k_canon_kept, grid_for(nd), dim3(256), 0, s, d_status, d_first, d_out_len, nd, kept, ok);
@@ -209,8 +235,9 @@ void canon_compact_device(hipStream_t s, const int* d_status, const unsigned lon
   hip_check(hipStreamSynchronize(s), "canonical compaction");
   *n_cr = (uint32_t)tot[0]; *n_cg = (uint32_t)tot[1];
   c_off.reserve((size_t)tot[0] * 8 + 8); c_len.reserve((size_t)tot[0] * 4 + 4); c_grp.reserve((size_t)(tot[1] + 1) * 4); c_def.reserve((size_t)tot[1] * 4 + 4);
+  if (d_runs) c_runs->reserve((size_t)(tot[0] + 1) * sizeof(canon::RefRuns));
   hipLaunchKernelGGL(k_canon_lists, grid_for(nd), dim3(256), 0, s, d_status, d_first, d_out_off, d_out_len, nd, rbase, gidx, c_off.as<uint64_t>(), c_len.as<uint32_t>(),
-                     c_grp.as<uint32_t>(), c_def.as<uint32_t>());
+                     c_grp.as<uint32_t>(), c_def.as<uint32_t>(), d_runs, d_runs ? c_runs->as<canon::RefRuns>() : nullptr);
   hip_check(hipGetLastError(), "k_canon_lists launch");
 }
 

@@ -181,6 +181,7 @@ struct fgx_caller {
   fgx::DevBuf d_res_out1, d_res_off1, d_res_final, d_res_aux, d_res_aux2, d_res_deferred, d_res_scan, d_res_cdef, d_res_outoff;   // canonical second pass inside the device-resident entry
   fgx::DevBuf d_canon_aux, d_canon_slabs;   // device canonicalisation (canon_device.hip): slot tables / status / lengths, per-lane lists
   fgx::DevBuf d_canon_blob, d_canon_off, d_canon_len, d_canon_grp;   // canonical duplex molecules of the second device pass (canon_core.h)
+  fgx::DevBuf d_canon_runs, d_canon_cruns;  // ... in the methylation-aware mode (FGX_METH_CANON=1): the reference runs of every slot / of the canonical batch's records
   fgx::FilterBuffers* filt = nullptr;      // fgx_filter_records[_device] state (filter.hip)
   std::vector<uint8_t> rejects_host;       // host entry: the device-made rejects of the last batch (FGX_REJECTS_DEVICE=1)
   const uint64_t* last_group_off = nullptr; uint32_t last_group_stride = 0;   // device-resident entry: byte offset of group g in its record stream = last_group_off[g * stride] (device memory; nullptr: none)

@@ -231,6 +231,8 @@ struct FastPath {
   uint32_t last_deep_families = 0;         // ... of which k_deep_parse + k_deep_cols (simplex_deep.inc) took
   DevBuf d_deep_sizes, d_deep_row0, d_deep_rows, d_deep_fams, d_deep_out, d_deep_out2;
   DevBuf d_mflag, d_mu, d_mt, d_mslot, d_mcontigs;   // methylation-aware mode: per-column annotation, per-slot tag sizes, the contig table
+  const void* ref_runs = nullptr;          // methylation-aware mode, the canonical second pass (FGX_METH_CANON=1): canon::RefRuns of every record of the batch `run` is
+                                           // about to take, device memory; set by the caller around that one `run`, null otherwise (the records lie where they say)
   uint32_t last_meth_device = 0;           // families of the last batch that the device pipeline decided in the methylation-aware mode
   uint32_t last_meth_clipped = 0;          // ... of which held a record of more than one CIGAR op (clips around one aligned block) and were not deferred
   uint32_t last_routed = 0;                // families the split pipeline handed to the k_simplex_wave2 chain in the last batch

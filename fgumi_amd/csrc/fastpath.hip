@@ -43,6 +43,7 @@
 #include <hipcub/hipcub.hpp>
 #endif
 #include "bamrec.h"
+#include "canon_core.h"
 #include "engine.h"
 #include <cstdlib>
 #include <memory>
@@ -1067,6 +1068,16 @@ __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long u) 
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
   return ((unsigned long long)hi << 32) | lo;
 }
+// Methylation-aware mode, the canonical second pass (FGX_METH_CANON=1): the reference runs of record `rec` of the batch — its canon::RefRuns as dwords, read
+// through the scalar unit (constant address space: the canonical pass wrote them a kernel boundary ago) — or null when the batch carries none.  The
+// table's address is the word behind the contig lengths (contig_len[n_ref]; fill_params writes it with every batch), so that FastParams stays as it is.
+// `rec` is wave-uniform.
+typedef const FGX_CONST_AS uint32_t* RefRunsPtr;
+__device__ __forceinline__ RefRunsPtr meth_ref_runs(const FastParams& P, uint32_t rec) {
+  const unsigned long long tab = uniform_u64(P.contig_len[P.n_ref]);
+  if (!tab) return nullptr;
+  return (RefRunsPtr)(uintptr_t)uniform_u64(tab + (unsigned long long)rec * sizeof(canon::RefRuns));
+}
 __device__ __forceinline__ double uniform_f64(double v) {
   const unsigned long long u = (unsigned long long)__double_as_longlong(v);
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
@@ -1994,9 +2005,15 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     // p lies at the anchor's pos + p (forward) or at pos + T - 1 - p (reverse: the columns run in read orientation; with trailing clips that is NOT the
     // last aligned base).  The strand of the call is is_top_strand of the anchor's flags (methylation.rs:392-398): C / T against a reference C, else G / A
     // against a reference G.  No annotation (no tags from this call, nothing normalised) when the anchor names no contig of the genome handed over.
+    // The canonical second pass of the mode (FGX_METH_CANON=1; meth_ref_runs) hands over records that no longer lie where they say — `<len>M`, R2 on another
+    // reference id — with each record's REFERENCE RUNS (canon_core.h RefRuns: query_to_ref_positions on the original record): then the anchor's contig, strand
+    // step and column -> reference position come from its runs, and a column outside every run (an insertion) is no reference cytosine.  The anchor is
+    // wave-uniform, so its runs are read through a uniform address in a loop of uniform trip count.
     bool ann = false, a_rev = false;
     long long a_ref0 = 0;
     unsigned long long g_off = 0, g_len = 0;
+    RefRunsPtr a_runs = nullptr;                                   // (METH) the anchor's RefRuns as dwords, when the batch carries them
+    uint32_t a_nruns = 0;
     uint32_t tcode = 0, vcode = 0, target = 0;                     // unconverted / converted read base as 4-bit codes in consensus orientation; the reference base
     if constexpr (METH != 0) {
       const unsigned long long lm = members & __ballot(final_len == elen[k]);
@@ -2006,14 +2023,31 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       a_rev = (a_flags & bam::F_REVERSE) != 0;
       const bool a_top = a_rev == ((a_flags & bam::F_LAST) != 0);
       tcode = a_top ? 2u : 4u; vcode = a_top ? 8u : 1u; target = a_top ? (uint32_t)'C' : (uint32_t)'G';
-      ann = a_ref >= 0 && a_pos >= 0 && (uint32_t)a_ref < P.n_ref;
+      int32_t a_contig = a_ref;
+      bool placed = a_pos >= 0;
+      a_runs = meth_ref_runs(P, r0 + an);
+      if (a_runs) {
+        a_contig = (int32_t)uni(a_runs[0]);                        // the ORIGINAL reference id; -1: the record had no position
+        a_nruns = uni(a_runs[1]) & 0xFFu;
+        placed = a_contig >= 0;
+      }
+      ann = a_contig >= 0 && placed && (uint32_t)a_contig < P.n_ref;
       a_ref0 = a_rev ? (long long)a_pos + (long long)a_tot - 1 : (long long)a_pos;
-      if (ann) { g_off = uniform_u64(P.contig_off[a_ref]); g_len = uniform_u64(P.contig_len[a_ref]); }
+      if (ann) { g_off = uniform_u64(P.contig_off[a_contig]); g_len = uniform_u64(P.contig_len[a_contig]); }
       ann_set[k] = ann;
     }
     auto ref_is_c = [&](uint32_t p) -> bool {                      // the reference shows a cytosine of the call's strand under column p
       if (!ann) return false;
-      const long long rp = a_rev ? a_ref0 - (long long)p : a_ref0 + (long long)p;
+      long long rp = a_rev ? a_ref0 - (long long)p : a_ref0 + (long long)p;
+      if (a_runs) {
+        rp = -1;
+        for (uint32_t r = 0; r < a_nruns; r++) {                   // (uniform trip count; the runs are disjoint)
+          const uint32_t q0 = a_runs[2 + 4 * r], rl = a_runs[3 + 4 * r];
+          const long long f0 = (long long)(((unsigned long long)a_runs[5 + 4 * r] << 32) | a_runs[4 + 4 * r]);
+          const uint32_t d = p - q0;
+          if (p >= q0 && d < rl) rp = a_rev ? f0 - (long long)d : f0 + (long long)d;
+        }
+      }
       if (rp < 0 || (unsigned long long)rp >= g_len) return false;
       uint32_t rb = P.genome[g_off + (unsigned long long)rp];
       if (rb >= 'a' && rb <= 'z') rb -= 32;
@@ -4318,6 +4352,7 @@ struct Batch {
   unsigned long long* misc = nullptr;
   uint32_t* cnt(MiscWord w) const { return (uint32_t*)(misc + w); }
   FastParams P;                             // the kernels' parameters; a launch works on a copy with its list and slice
+  uint64_t runs_word = 0;                   // methylation-aware mode: the word behind the contig table (meth_ref_runs)
   // the split pipeline: families per wavefront of the record kernel, chunks, families per chunk; the record kernel's parameters
   uint32_t fpw = 0, n_chunks = 0, chunk_fam_raw = 0, chunk_fam = 0;
   FastParams PK;
@@ -4485,6 +4520,8 @@ struct Batch {
         hip_check(hipMemcpyAsync(fp.d_mcontigs.p, gr->off.data(), (size_t)n_ref * 8, hipMemcpyHostToDevice, s), "H2D contig offsets");
         hip_check(hipMemcpyAsync(fp.d_mcontigs.as<uint64_t>() + n_ref, gr->len.data(), (size_t)n_ref * 8, hipMemcpyHostToDevice, s), "H2D contig lengths");
       }
+      runs_word = (uint64_t)(uintptr_t)fp.ref_runs;      // behind the lengths: the batch's reference runs (meth_ref_runs), null outside the canonical second pass
+      hip_check(hipMemcpyAsync(fp.d_mcontigs.as<uint64_t>() + 2 * (size_t)n_ref, &runs_word, 8, hipMemcpyHostToDevice, s), "H2D reference runs table");
       P.meth_mode = o.methylation_mode; P.n_ref = n_ref; P.genome = (const uint8_t*)gr->d_genome.p;
       P.contig_off = fp.d_mcontigs.as<uint64_t>(); P.contig_len = fp.d_mcontigs.as<uint64_t>() + n_ref;
       P.meth_flag = fp.d_mflag.as<uint8_t>(); P.meth_u = fp.d_mu.as<uint16_t>(); P.meth_t = fp.d_mt.as<uint16_t>();

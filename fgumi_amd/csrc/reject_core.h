@@ -119,7 +119,7 @@ CANON_HD uint32_t trim_point(const uint8_t* q, uint32_t n, bool rev, uint8_t tri
 }
 
 // create_source_read (vanilla_caller.rs:1080-1190) as far as the filters need it: the read's final length (quality trimming, masking, the
-// mate clip, the trailing no-call strip) and its simplified CIGAR (reversed for reverse reads, truncated to the final length) in R.
+// mate clip — kept in R.clip, at most l_seq —, the trailing no-call strip) and its simplified CIGAR (reversed for reverse reads, truncated to the final length) in R.
 // 1 = a source read, 0 = dropped (zero length), -1 = out of scope (qualities the reference refuses, an MC tag of too many ops).
 CANON_HD int source_info(uint8_t min_bq, bool trim, const bam::Rec& v, canon::ReadInfo& R, canon::Scratch& C) {
   const uint32_t l = v.l_seq(), nc = v.n_cigar();
@@ -137,6 +137,7 @@ CANON_HD int source_info(uint8_t min_bq, bool trim, const bam::Rec& v, canon::Re
   bool overflow = false;
   const uint64_t clip = bam::mate_clip(v, C.ops, nc, mco >= 0 ? v.b + v.aux_off() + mco : nullptr, mcl, C.mc_ops, canon::MAX_OPS + 1, &overflow);
   if (overflow) return -1;
+  R.clip = clip > l ? l : (uint32_t)clip;
   const bool rev = (v.flags() & bam::F_REVERSE) != 0;
   const uint32_t trim_to = trim ? trim_point(q, l, rev, min_bq) : l;
   const uint32_t clip_pos = (uint64_t)l > clip ? l - (uint32_t)clip : 0;
@@ -290,6 +291,101 @@ CANON_HD void emit_rejects(const uint8_t* blob, const uint64_t* rec_off, const u
   }
 }
 
+
+}  // namespace rej
+
+// =====================================================================================================================================
+// The canonical form of a SIMPLEX family whose reads carry indels / skips / pads (canon_core.h has the duplex and CODEC forms; this one
+// lives here because it is built from the gate restatement above: source_info, the order of process_group / process_subgroup).
+//
+// Per end (fragment / R1 / R2) the reference does what the duplex form's head comment lists — overlap pre-correction on the LAST R1 and
+// LAST R2 of a name, mate clip, final length, alignment filter on the simplified CIGARs — and after them a source read is a string of
+// bases.  The survivors get `<len>M`, lose MC, R2 moves to the other reference id; `Delta` counts the filter's drops and the
+// pre-step's CorrectionStats.  What has to be restated exactly is the ORDER of the gates: the alignment filter runs on an
+// end only where the reference reaches it — the whole group and the raw subgroup hold --min-reads records, and so do the subgroup's
+// reads of non-zero length — since a read the reference counts as InsufficientReads must not be counted as MinorityAlignment here.
+// A biting --max-reads is in scope: it is decided after the filter, on the survivors, which is what the kernels are given.
+// Out of scope: --trim, unmapped / secondary / supplementary records, more than MAX_READS records / MAX_OPS ops / MAX_GROUPS alignment
+// groups, records the reference refuses, a group below --min-reads (rejected whole either way), and the two cases in which the
+// canonical family would be rejected at an EARLIER gate than the original (see below).
+// `runs` (methylation-aware mode, else null): runs[i] = the reference runs of surviving record i (canon::RefRuns).
+namespace canon {
+
+CANON_HD int canon_simplex_family(const rej::Params& P, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out,
+                                  const uint64_t* out_off, uint32_t* out_len, rej::Scratch& S, Delta& D, RefRuns* runs = nullptr) {
+  D.minority = 0; D.ov[0] = D.ov[1] = D.ov[2] = D.ov[3] = 0;
+  if (n == 0 || n > MAX_READS || P.trim) return CANON_OUT_OF_SCOPE;
+  if (n < P.min_reads) return CANON_OUT_OF_SCOPE;                        // simplex.rs:673-683: rejected whole, before the pre-step
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t len = rec_len[i];
+    if (len < 32) return CANON_OUT_OF_SCOPE;
+    bam::Rec v{blob + rec_off[i], len};
+    const uint16_t f = v.flags();
+    const uint32_t nc = v.n_cigar(), l = v.l_seq();
+    if (v.l_read_name() == 0 || (uint64_t)v.aux_off() > len) return CANON_OUT_OF_SCOPE;
+    if (f & (bam::F_UNMAPPED | bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) return CANON_OUT_OF_SCOPE;
+    if ((f & bam::F_PAIRED) && ((f & bam::F_FIRST) != 0) == ((f & bam::F_LAST) != 0)) return CANON_OUT_OF_SCOPE;
+    if (nc == 0 || nc > MAX_OPS) return CANON_OUT_OF_SCOPE;
+    uint64_t ql = 0;
+    for (uint32_t k = 0; k < nc; k++) { const uint32_t op = v.cigar_op(k); if ((op & 0xF) > 8) return CANON_OUT_OF_SCOPE; if (bam::op_consumes_query(op & 0xF)) ql += op >> 4; }
+    if (ql != l) return CANON_OUT_OF_SCOPE;
+    S.cls[i] = !(f & bam::F_PAIRED) ? 1 : (f & bam::F_FIRST) ? 2 : 3;
+    uint8_t* w = out + out_off[i];
+    for (uint32_t k = 0; k < len; k++) w[k] = v.b[k];
+    out_len[i] = len;
+  }
+  // the overlap pre-step (simplex.rs:685-700; apply_overlapping_consensus pairs the LAST R1 and the LAST R2 of a name)
+  if (P.overlapping) {
+    for (uint32_t i = 0; i < n; i++) {
+      if (S.cls[i] == 1) continue;
+      bam::Rec vi{out + out_off[i], rec_len[i]};
+      bool seen = false;
+      for (uint32_t j = 0; j < i && !seen; j++) seen = S.cls[j] != 1 && names_equal(vi, bam::Rec{out + out_off[j], rec_len[j]});
+      if (seen) continue;
+      int64_t r1 = -1, r2 = -1;
+      for (uint32_t j = i; j < n; j++) {
+        if (S.cls[j] == 1 || !names_equal(vi, bam::Rec{out + out_off[j], rec_len[j]})) continue;
+        if (S.cls[j] == 2) r1 = j; else r2 = j;
+      }
+      if (r1 >= 0 && r2 >= 0) overlap_pair(out + out_off[r1], rec_len[r1], out + out_off[r2], rec_len[r2], S.c.ops, D.ov);
+    }
+  }
+  // every record's clip, final length and simplified CIGAR (create_source_read :1080-1190), of the corrected copies
+  for (uint32_t i = 0; i < n; i++) {
+    const int sr = rej::source_info(P.min_bq, false, bam::Rec{out + out_off[i], rec_len[i]}, S.c.r[i], S.c);
+    if (sr < 0) return CANON_OUT_OF_SCOPE;                               // (R.clip: the cut of the canonical record; R.keep = 1)
+  }
+  // process_subgroup (:1454-1646), per end, up to the alignment filter
+  for (uint32_t c = 1; c <= 3; c++) {
+    uint32_t m = 0, ns = 0;
+    for (uint32_t i = 0; i < n; i++) if (S.cls[i] == c) { m++; if (S.c.r[i].final_len > 0) S.c.list[ns++] = i; }
+    if (m == 0 || m < P.min_reads) continue;                             // InsufficientReads: every record stays, the pass counts them the same
+    if (ns < P.min_reads) continue;                                      // ZeroLength, then InsufficientReads: likewise
+    const int rj = alignment_filter(S.c, ns);
+    if (rj < 0) return CANON_OUT_OF_SCOPE;
+    if (rj > 0) {
+      D.minority += (uint64_t)rj;
+      // the canonical end has m - rj records: below --min-reads the pass rejects them BEFORE it looks for reads of zero length, the
+      // reference after — with such a read in the end the two counts differ
+      if (m - (uint32_t)rj < P.min_reads && ns != m) return CANON_OUT_OF_SCOPE;
+    }
+  }
+  if (D.minority && (uint64_t)n - D.minority < P.min_reads) return CANON_OUT_OF_SCOPE;   // the canonical GROUP would be rejected whole
+  for (uint32_t i = 0; i < n; i++) {
+    if (!S.c.r[i].keep) { out_len[i] = 0; continue; }
+    if (runs) {
+      bam::Rec v{out + out_off[i], rec_len[i]};
+      const uint32_t nc = v.n_cigar();
+      for (uint32_t k = 0; k < nc; k++) S.c.ops[k] = v.cigar_op(k);
+      ref_runs_of(S.c.r[i].simp, S.c.r[i].n_simp, S.c.ops, nc, v.ref_id(), v.pos(), (v.flags() & bam::F_REVERSE) != 0, runs[i]);
+    }
+    out_len[i] = rewrite_record(out + out_off[i], rec_len[i], S.c.r[i].clip, S.cls[i] == 3);
+  }
+  return CANON_OK;
+}
+
+}  // namespace canon
+namespace rej {
 
 // =====================================================================================================================================
 // The duplex caller's rejects (duplex_caller.rs:1944-2120, 2545-2610; src/lib/commands/duplex.rs:742-830).  What it writes for a

@@ -63,7 +63,9 @@ struct DeepFam {            // 64 bytes
   uint32_t a_info[2];       // contig | annotated << 28 | step is -1 << 29 | is_top_strand(anchor) << 30 | is_top_strand(first retained read) << 31
   uint32_t rej_down;        // retained reads that --max-reads dropped
   uint32_t clipped;         // methylation-aware mode: a record of the family has more than one CIGAR op (k_deep_cols<1> counts the family once it is decided)
-  uint32_t _pad[5];
+  uint32_t a_rec[2];        // methylation-aware mode, the canonical second pass (FGX_METH_CANON=1): per end the anchor's record index in the batch + 1 — k_deep_cols<1> looks
+                            // the reference base up through that record's reference runs (canon::RefRuns, meth_ref_runs) instead of the one a_ref0 run; 0: no runs given
+  uint32_t _pad[3];
 };
 static_assert(sizeof(DeepRow) == 32 && sizeof(DeepFam) == 96, "deep descriptors");
 
@@ -561,13 +563,23 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
         if (a < 0) continue;
         const uint32_t ua = (uint32_t)a;
         const bool rv = (S.bits[ua] & 4u) != 0;
-        const bool placed = S.ref_id[ua] >= 0 && S.pos[ua] >= 0 && (uint32_t)S.ref_id[ua] < P.n_ref;
+        bool placed = S.ref_id[ua] >= 0 && S.pos[ua] >= 0 && (uint32_t)S.ref_id[ua] < P.n_ref;
+        uint32_t contig = (uint32_t)S.ref_id[ua];
+        if constexpr (CLIPS != 0) {                          // (the builds of the mode) a canonical batch: the record no longer lies where it says — its runs name the contig
+          const unsigned long long tab = P.contig_len[P.n_ref];
+          if (tab) {
+            const int32_t rid = ((const canon::RefRuns*)(uintptr_t)tab)[r0 + ua].ref_id;      // the ORIGINAL reference id; -1: the record had no position
+            placed = rid >= 0 && (uint32_t)rid < P.n_ref;
+            contig = (uint32_t)rid;
+            f.a_rec[k] = r0 + ua + 1u;
+          }
+        }
         // query_to_ref_positions (methylation.rs:116-184) on the ONE M op the reference makes of the read: a forward anchor's column p lies at pos + p —
         // a leading clip shifts the lookup, as it does there —, a reverse anchor's at pos + T - 1 - p, T = the lengths of all its ops (l_seq when it
         // is one op; with hard clips more than l_seq)
         if constexpr (CLIPS != 0) f.a_ref0[k] = rv ? S.pos[ua] + (int32_t)S.tot[ua] - 1 : S.pos[ua];
         else f.a_ref0[k] = rv ? S.pos[ua] + (int32_t)S.l_seq[ua] - 1 : S.pos[ua];
-        f.a_info[k] = (placed ? ((uint32_t)S.ref_id[ua] & 0x0FFFFFFFu) | (1u << 28) : 0u) | (rv ? 1u << 29 : 0u) | (top_of(ua) ? 1u << 30 : 0u) | (top_of((uint32_t)first) ? 1u << 31 : 0u);
+        f.a_info[k] = (placed ? (contig & 0x0FFFFFFFu) | (1u << 28) : 0u) | (rv ? 1u << 29 : 0u) | (top_of(ua) ? 1u << 30 : 0u) | (top_of((uint32_t)first) ? 1u << 31 : 0u);
       }
     }
     *F = f;
@@ -688,9 +700,24 @@ __global__ __launch_bounds__(256, FGX_DEEP_OCC) void k_deep_cols(FastParams P, D
     const uint32_t tcode = atop ? 2u : 4u, vcode = atop ? 8u : 1u, target = atop ? (uint32_t)'C' : (uint32_t)'G';
     unsigned long long g_off = 0, g_len = 0;
     if (annotated) { g_off = uniform_u64(P.contig_off[ainfo & 0x0FFFFFFFu]); g_len = uniform_u64(P.contig_len[ainfo & 0x0FFFFFFFu]); }
+    // a canonical batch (FGX_METH_CANON=1): the anchor's reference runs instead of the one run from a_ref0 — the anchor is wave-uniform, so are its runs:
+    // scalar loads, a loop of uniform trip count; a column outside every run (an insertion) is no reference cytosine
+    const uint32_t arec = METH ? uni(Fp->a_rec[k]) : 0u;
+    RefRunsPtr a_runs = nullptr;
+    uint32_t a_nruns = 0;
+    if (arec) { a_runs = meth_ref_runs(P, arec - 1u); if (a_runs) a_nruns = uni(a_runs[1]) & 0xFFu; }
     auto ref_is_c = [&](uint32_t p) -> bool {
       if (!annotated) return false;
-      const long long rp = (long long)aref0 + (((ainfo >> 29) & 1u) ? -(long long)p : (long long)p);
+      long long rp = (long long)aref0 + (((ainfo >> 29) & 1u) ? -(long long)p : (long long)p);
+      if (a_runs) {
+        rp = -1;
+        for (uint32_t r = 0; r < a_nruns; r++) {
+          const uint32_t q0 = a_runs[2 + 4 * r], rl = a_runs[3 + 4 * r];
+          const long long f0 = (long long)(((unsigned long long)a_runs[5 + 4 * r] << 32) | a_runs[4 + 4 * r]);
+          const uint32_t d = p - q0;
+          if (p >= q0 && d < rl) rp = ((ainfo >> 29) & 1u) ? f0 - (long long)d : f0 + (long long)d;
+        }
+      }
       if (rp < 0 || (unsigned long long)rp >= g_len) return false;
       uint32_t rb = P.genome[g_off + (unsigned long long)rp];
       if (rb >= 'a' && rb <= 'z') rb -= 32;

@@ -222,6 +222,21 @@ int fgx_methylation_mm_ml_host(const uint8_t* bases, uint32_t n, const uint8_t* 
  * source compiles for the device (one lane per molecule). */
 int fgx_canon_duplex_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
                           uint64_t* delta5);
+/* The same, with the REFERENCE RUNS the canonical pass emits in the methylation-aware mode (FGX_METH_CANON=1): for every surviving record i,
+ * runs[i * FGX_CANON_RUNS_WORDS ..] = {original ref_id (-1: no position), number of runs | REVERSE bit << 31, then per run: first column, length,
+ * reference position of the first column (int64, low dword first)} — query_to_ref_positions (methylation.rs:116-178) on the ORIGINAL record, the
+ * position stepping down for a reverse record.  The canonical record itself no longer shows its place (`<len>M`, R2 on another reference id). */
+#define FGX_CANON_RUNS_WORDS 34
+int fgx_canon_duplex_runs_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
+                               uint64_t* delta5, uint32_t* runs);
+/* The canonical form of ONE SIMPLEX family (fgumi_amd/csrc/reject_core.h `canon_simplex_family`): per end (fragment / R1 / R2) the overlap pre-correction
+ * on the LAST R1 and LAST R2 of a name (simplex.rs:685-700), the mate clip, the final length and the alignment filter, in the ORDER of the reference's gates
+ * (the filter runs on an end only where the whole group, the raw subgroup and its reads of non-zero length hold --min-reads: vanilla_caller.rs:1329-1646);
+ * survivors get `<len>M`, lose MC, R2 moves to the other reference id; delta5 as above.  A biting --max-reads is in scope (decided after the filter, by the
+ * pass).  Out of scope (1): --trim, unmapped / secondary / supplementary records, more than 128 records / 16 ops / 16 alignment groups, records the
+ * reference refuses, a group below --min-reads.  `runs` may be NULL; else the reference runs of every surviving record as for the duplex hook. */
+int fgx_canon_simplex_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
+                           uint64_t* delta5, uint32_t* runs);
 /* The same for ONE CODEC molecule (codec_caller.rs:625-1262): every read cut by its virtual clip against the mate in hand
  * (raw-bam/cigar.rs:404-446), `<len>M`, and PLACED so that the one-M-op CODEC kernels recompute the original's overlap geometry — the
  * consensus length above all (query positions at the end of the shared window, cigar.rs:461-500).  Every record is kept (the consensus
