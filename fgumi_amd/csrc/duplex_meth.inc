@@ -1,6 +1,6 @@
 // duplex_meth.inc — the methylation tags of a duplex consensus record in the device-resident pipeline (methylation-aware mode: EM-Seq / TAPs).
 // Included by fastpath.hip inside `namespace fgx { namespace {` after simplex_deep.inc (meth_chunk_skip, meth_digits) and the duplex record writers
-// (duplex_combine).
+// (duplex_call).
 //
 // What comes before: k_family_wave<1, 1> left, per scratch column of each of the molecule's four read sets, "the reference shows a cytosine of the
 // call's strand" and the unconverted / converted counts (FastParams::meth_flag / meth_u / meth_t), called the NORMALISED reads, and said in
@@ -14,7 +14,7 @@
 // and nothing at all when no strand of the record is annotated.  An MM string (build_mm_ml_tags, methylation.rs:264-343) lists, for every base of the
 // sequence that is the strand's cytosine (C on C+m, G on G-m) and has evidence (reference cytosine, unconverted + converted > 0), how many such bases
 // without evidence were skipped since the previous entry; a string without an entry is not written (its count arrays still are).  The duplex MM is
-// built from the duplex bases: duplex_combine, the same function the record writers call.
+// built from the duplex bases: duplex_call, the same function the record writers call.
 //
 // Two kernels in the shape of k_meth_sizes / k_meth_tail (simplex_deep.inc), a wavefront per record, 64 columns per step: k_duplex_meth_sizes after
 // k_call_full and before the scan of the record sizes (the strings depend on final bases), k_duplex_meth_tail after the record writers.
@@ -29,10 +29,7 @@ __device__ __forceinline__ DMethCol duplex_meth_col(const FastParams& P, uint64_
   const uint32_t ca = P.col_code[oa], cb = P.col_code[ob], qa = P.col_qual[oa], qb = P.col_qual[ob];
   c.flag = (uint32_t)(P.meth_flag[oa] | P.meth_flag[ob]);            // (a strand without an annotation has no flag set and no count)
   c.u = (uint32_t)P.meth_u[oa] + P.meth_u[ob]; c.t = (uint32_t)P.meth_t[oa] + P.meth_t[ob];   // (at most 64 reads per strand: no saturation to apply)
-  uint32_t rb, rq;
-  bool artifact;
-  duplex_combine<1>(ca, qa, cb, qb, c.flag != 0, rb, rq, artifact);
-  c.code = (ca == 15 || cb == 15 || rq == FGX_MIN_PHRED) ? 15u : rb;
+  c.code = duplex_call<1>(ca, qa, cb, qb, c.flag != 0).oc;
   return c;
 }
 // which sequences of a record carry tags: bit 0 the AB-side strand, bit 1 the BA-side strand, bit 2 the combined annotation

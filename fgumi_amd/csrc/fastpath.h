@@ -191,7 +191,7 @@ struct DuplexEmitParams {
   const uint8_t* col_code; const uint8_t* col_qual; const uint16_t* col_err; const uint32_t* col_obs;
   const char* prefix; uint32_t prefix_len; const char* rg; uint32_t rg_len;
   uint8_t per_base_tags; char cell0, cell1;
-  uint32_t* n_slow;                // k_count_slow_duplex counts the valid records the fast writer leaves to the per-field kernel here (0: that kernel is not launched at all)
+  uint32_t* n_slow;                // k_count_slow counts the valid records the fast writer leaves to the per-field kernel here (0: that kernel is not launched at all)
   const uint8_t* meth_flag;        // methylation-aware mode (the <1> builds of the writers): per column, the reference shows a cytosine of the strand's call
   const uint32_t* col_obs_all;     // a caller with --max-reads-per-strand (the CAP builds of the writers): the recount source of the records with DuplexDesc::capped
 };
@@ -204,7 +204,7 @@ struct CodecEmitParams {
   uint8_t per_base_tags; char cell0, cell1;
   uint8_t has_outer, outer_qual, has_ss, ss_qual; uint32_t outer_len;
   unsigned long long* stats;       // slot-spread counters: [24] consensus bases, [25] duplex bases, [26] disagreeing duplex bases
-  uint32_t* n_slow;                // k_count_slow_codec counts the valid records the fast writer leaves to the per-field kernel here
+  uint32_t* n_slow;                // k_count_slow counts the valid records the fast writer leaves to the per-field kernel here
 };
 
 struct FastResult {

@@ -169,3 +169,24 @@ def test_long_read_name_prefix_takes_the_per_field_writer():
     """(round 6) k_emit_codec is launched only when the fast writer counted records it refuses (and the base counters are reduced again behind it)."""
     from fgumi_amd import simulate_grouped_reads
     _same(simulate_grouped_reads(200, family_size=3, read_length=150, insert_mean=200, insert_sd=30, codec=1), prefix="c" * 70)
+
+
+def test_one_batch_for_the_fast_and_the_per_field_writer():
+    """A 60-character prefix: the name crosses 64 bytes between two- and three-digit MIs — k_emit_codec_fast and k_emit_codec both own records of the batch."""
+    from test_wavemu_record_writers import CODEC_SIM, writer_counts
+    _, want = _same(simulate_grouped_reads(200, **CODEC_SIM), prefix="p" * 60)
+    fast, slow = writer_counts(want["data"])
+    assert fast > 0 and slow > 0, (fast, slow)
+
+
+def test_per_field_writer_with_both_orientations_and_the_quality_masks():
+    """k_emit_codec (a 70-character prefix) with per-base tags and both quality masks on, on molecules of both orientations of R1; the outer 90 bases reach
+    into the two-strand stretch, so the expected output shows both masks."""
+    from test_wavemu_record_writers import CODEC_SIM, r1_orientations, writer_counts
+    g = simulate_grouped_reads(200, **CODEC_SIM)
+    assert r1_orientations(g) == {False, True}
+    _, want = _same(g, prefix="c" * 70, produce_per_base_tags=True, single_strand_qual=4, outer_bases_qual=5, outer_bases_length=90)
+    recs = [bamutil.parse(r) for r in split_records(want["data"])]
+    assert writer_counts(want["data"]) == (0, len(recs)) and len(recs) > 100
+    assert all(set(r["quals"][:90] + r["quals"][-90:]) <= {4, 5} for r in recs)
+    assert sum("n" in r["tags"]["ac"][1] + r["tags"]["bc"][1] and 4 in r["quals"] and 5 in r["quals"] for r in recs) > len(recs) // 2

@@ -147,3 +147,18 @@ def test_long_read_name_prefix_takes_the_per_field_writer():
     read-name prefix makes it refuse every record."""
     from fgumi_amd import simulate_grouped_reads
     _same(simulate_grouped_reads(200, family_size=6, duplex=1), prefix="d" * 70)
+
+
+def test_one_batch_for_the_fast_and_the_per_field_writer():
+    """A 60-character prefix: the name crosses 64 bytes between two- and three-digit MIs — k_emit_duplex_fast and k_emit_duplex both own records of the batch."""
+    from test_wavemu_record_writers import DUPLEX_SIM, writer_counts
+    out = _same(simulate_grouped_reads(200, **DUPLEX_SIM), prefix="p" * 60)
+    fast, slow = writer_counts(out.data)          # (the oracle's bytes: _same compared them)
+    assert fast > 0 and slow > 0, (fast, slow)
+
+
+def test_records_above_256_positions_take_the_per_field_writer():
+    """Reads of 300 bases under the default prefix: k_emit_duplex_fast refuses the records for their length alone."""
+    from test_wavemu_record_writers import LONG_DUPLEX_SIM
+    out = _same(simulate_grouped_reads(60, **LONG_DUPLEX_SIM))
+    assert sum(len(bamutil.parse(r)["seq"]) > 256 for r in split_records(out.data)) > 60

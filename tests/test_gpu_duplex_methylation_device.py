@@ -203,6 +203,17 @@ def test_opt_out_sends_the_batch_through_the_general_path(monkeypatch):
     assert off["meth_device"] == 0 and off["data"] == on["data"], (off["meth_device"], off["deferred"])
 
 
+def test_long_read_name_prefix_takes_the_per_field_writer():
+    """k_emit_duplex<1> — the per-field writer's methylation build — with records it accepts: the smallest batch here under a 70-character prefix, every
+    group decided on the device."""
+    from test_wavemu_record_writers import writer_counts
+    contigs, groups = batch(1, plain=True, n_groups=400)
+    g = GroupedReads.from_groups(groups)
+    got, want = same_through_the_host_entry(options(1, (1, 1, 0), read_name_prefix=b"m" * 70), contigs, g)
+    assert got["meth_device"] == g.n_grp and got["deferred"] == 0, got
+    assert writer_counts(want["data"]) == (0, want["count"]) and tag_counts(want["data"])["mm"] > 100
+
+
 # ---- 5. file -> file -------------------------------------------------------------------------------------------------------------------------------------
 def test_run_bam_keeps_the_batches_on_the_device(tmp_path):
     from fgumi_amd import bgzf

@@ -132,6 +132,22 @@ def check_run_bam(kind, cap, tmp_dir, n=3000):
     c.close()
 
 
+def check_per_field_writer_cap_build():
+    """k_emit_duplex<0, 1> — the per-field writer's CAP build — with a record whose recount reads the all-reads counts: the crafted molecule of
+    tests/test_wavemu_strand_cap.py whose dropped read is the only one that disagrees, under a 70-character prefix, decided on the device."""
+    import bamutil
+    from fgumi_amd import split_records
+    from test_gpu_duplex_methylation_device import same_through_the_host_entry
+    from test_wavemu_record_writers import cap_changes_the_recount, capped_molecule, writer_counts
+    g = capped_molecule()
+    kw = dict(kind=1, read_name_prefix=b"k" * 70)
+    got, want = same_through_the_host_entry(fgx_opts.defaults(duplex_max_reads_per_strand=2, **kw), None, g)
+    assert got["deferred"] == 0, got
+    assert writer_counts(want["data"]) == (0, want["count"])
+    off = orc.process(fgx_opts.defaults(**kw), g.blob, g.rec_off, g.rec_len, g.grp_first, batch_groups=100)
+    cap_changes_the_recount(*([bamutil.parse(r) for r in split_records(w["data"])] for w in (want, off)))
+
+
 @pytest.mark.parametrize("cap,min_reads", [(1, (1, 1, 0)), (3, (1, 1, 0)), (4, (3, 2, 1))], ids=["cap1", "cap3", "cap4_min_3_2_1"])
 def test_duplex_cap_on_the_device(cap, min_reads):
     run_isolated("test_gpu_strand_cap", "check_device_batch", 1, cap, min_reads, timeout=600)
@@ -159,3 +175,7 @@ def test_duplex_rejects_under_a_cap_stay_on_the_device():
 @pytest.mark.parametrize("kind,cap", [(1, 3), (2, 2)], ids=["duplex", "codec"])
 def test_run_bam_on_a_capped_file(kind, cap, tmp_path):
     run_isolated("test_gpu_strand_cap", "check_run_bam", kind, cap, str(tmp_path), timeout=600)
+
+
+def test_long_read_name_prefix_takes_the_per_field_writer_cap_build():
+    run_isolated("test_gpu_strand_cap", "check_per_field_writer_cap_build", timeout=600)

@@ -1,7 +1,8 @@
 """The device-resident pipeline's WAVEFRONT kernels, executed on the CPU in 64-lane lock-step (the wave-level host emulator).
 
-tests/wavemu compiles fgumi_amd/csrc/fastpath.hip — the host driver (run_once, the stages of Batch) and every kernel it launches (k_col_bound, k_split_parse, k_split_cols in
-its builds, k_split_finish, k_simplex_seg, k_simplex_wave2, k_family_wave, k_deep_*, k_family, k_call_full, k_emit*) — for the host under
+tests/wavemu compiles fgumi_amd/csrc/fastpath.hip and its include files — the host driver (run_once, the stages of Batch) and every kernel it launches (k_col_bound,
+k_split_parse, k_split_cols in its builds, k_split_finish, k_simplex_seg, k_simplex_wave2, k_family_wave, k_deep_*, k_family, k_call_full, and the record writers
+of record_writers.inc: k_emit*, k_count_slow) — for the host under
 tests/wavemu/simt.h: a fiber per thread, a rendezvous per cross-lane operation (__ballot, __shfl*, readlane, DPP, ds_bpermute, wave barriers,
 __syncthreads) evaluated with the hardware's semantics, LDS as arrays; everything else of the product's host side is tests/apiemu's (api.cpp
 unmodified on a fake HIP runtime).  `fgx_process_batch_device` on host arrays then runs the product's real launch chain and real kernel sources,
@@ -80,8 +81,8 @@ def test_other_simplex_shapes(case):
 
 @pytest.mark.parametrize("kind", [0, 1, 2], ids=["simplex", "duplex", "codec"])
 def test_per_field_record_writers(kind):
-    """A 70-character read-name prefix: the one-store field writers refuse every record — emit_generic / k_emit_duplex / k_emit_codec (the latter two launched
-    only because the fast writers counted what they refused)."""
+    """A 70-character read-name prefix: the one-store field writers refuse every record — emit_generic / k_emit_duplex / k_emit_codec of record_writers.inc (the
+    latter two launched only because k_count_slow counted what the fast writers refuse; their other builds and batches: tests/test_wavemu_record_writers.py)."""
     sim = [dict(family_size=5), dict(family_size=6, duplex=1), dict(family_size=3, read_length=150, insert_mean=200, insert_sd=30, codec=1)][kind]
     opts = dict(read_name_prefix=b"n" * 70, **(dict(overlapping_consensus=0) if kind == 2 else dict(min_reads=1)))
     run_isolated("test_wavemu", "check_device_entry", kind, 150, sim, opts, env=env(), timeout=900)
