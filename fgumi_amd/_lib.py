@@ -201,6 +201,9 @@ def load():
     L.fgx_debug_last_meth_device.restype = U32
     L.fgx_debug_last_meth_clipped.argtypes = [VP]
     L.fgx_debug_last_meth_clipped.restype = U32
+    if hasattr(L, "fgx_debug_last_wide_families"):          # (a library built before the wide kernels, loaded through FGX_LIB for a comparison, has none)
+        L.fgx_debug_last_wide_families.argtypes = [VP]
+        L.fgx_debug_last_wide_families.restype = U32
     L.fgx_set_general_only.argtypes = [VP, I]
     L.fgx_set_general_only.restype = None
     L.fgx_set_fast_lds_bytes.argtypes = [VP, U32]

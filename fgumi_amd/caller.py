@@ -339,6 +339,12 @@ class _HandleCaller(ConsensusCaller):
         record (more than one CIGAR op) and were decided by the device kernels."""
         return dict(on_device=int(lib.fgx_debug_last_meth_device(self._h)), clipped=int(lib.fgx_debug_last_meth_clipped(self._h)))
 
+    @property
+    def last_wide_families(self) -> int:
+        """Families of the last device batch that the wide kernels decided (FGX_DEEP_WIDE=1: more records, or more reads per end, than the
+        streaming kernels of deep families hold; up to 16 384 records)."""
+        return int(lib.fgx_debug_last_wide_families(self._h))
+
     def set_general_only(self, on: bool = True):
         """Route every family through the general host-orchestrated path (default: device-resident fast
         path, general path only for the families it defers)."""

@@ -230,6 +230,8 @@ struct FastPath {
   uint32_t last_big_families = 0;          // ... in the last batch
   uint32_t last_deep_families = 0;         // ... of which k_deep_parse + k_deep_cols (simplex_deep.inc) took
   DevBuf d_deep_sizes, d_deep_row0, d_deep_rows, d_deep_fams, d_deep_out, d_deep_out2;
+  uint32_t last_wide_families = 0;         // ... and of what those left, the wide kernels (simplex_wide.inc; FGX_DEEP_WIDE=1) took — not counted into last_deep_families
+  DevBuf d_wide_scratch, d_wide_pass, d_wide_pass0, d_wide_depth;   // k_wide_parse's per-record state, the families' column passes and their scan, the passes' depth extremes
   DevBuf d_mflag, d_mu, d_mt, d_mslot, d_mcontigs;   // methylation-aware mode: per-column annotation, per-slot tag sizes, the contig table
   const void* ref_runs = nullptr;          // methylation-aware mode, the canonical second pass (FGX_METH_CANON=1): canon::RefRuns of every record of the batch `run` is
                                            // about to take, device memory; set by the caller around that one `run`, null otherwise (the records lie where they say)

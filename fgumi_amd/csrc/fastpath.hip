@@ -2862,6 +2862,7 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
 #include "simplex_seg.inc"
 #include "simplex_split.inc"
 #include "simplex_deep.inc"
+#include "simplex_wide.inc"
 #include "duplex_meth.inc"
 
 // Upper bound on the consensus columns a batch can produce: a family yields at most three ends, each no
@@ -2935,7 +2936,7 @@ __global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, uns
 void FastPath::release() {
   for (DevBuf* b : {&d_ends, &d_sizes, &d_offsets, &d_code, &d_qual, &d_depth, &d_err, &d_misc, &d_deferred, &d_out, &d_scan_tmp, &d_strings, &d_obs, &d_obs_all, &d_retry2,
                     &d_retry, &d_bound, &d_colbase, &d_statslots, &d_full_items, &d_full_count, &d_retry_old, &d_w2img, &d_famdesc, &d_fwimg,
-                    &d_split_rec, &d_split_fam, &d_split_out, &d_route, &d_s2img, &d_dir_size, &d_dir_off, &d_dir_base, &d_slot_desc, &d_slot_err, &d_out2, &d_scan_tmp2, &d_big, &d_deep_sizes, &d_deep_row0, &d_deep_rows, &d_deep_fams, &d_deep_out, &d_deep_out2, &d_mflag, &d_mu, &d_mt, &d_mslot, &d_mcontigs})
+                    &d_split_rec, &d_split_fam, &d_split_out, &d_route, &d_s2img, &d_dir_size, &d_dir_off, &d_dir_base, &d_slot_desc, &d_slot_err, &d_out2, &d_scan_tmp2, &d_big, &d_deep_sizes, &d_deep_row0, &d_deep_rows, &d_deep_fams, &d_deep_out, &d_deep_out2, &d_wide_scratch, &d_wide_pass, &d_wide_pass0, &d_wide_depth, &d_mflag, &d_mu, &d_mt, &d_mslot, &d_mcontigs})
     b->free_();
   for (int i = 0; i < 4; i++) if (ev[i]) { (void)hipEventDestroy(ev[i]); ev[i] = nullptr; }
   if (s2) {
@@ -3007,6 +3008,8 @@ struct BatchSwitches {     // read at the start of every batch: tests and tools 
   const int split_mode = env_int(split_env, 1);
   const bool direct = env_is1(getenv("FGX_DIRECT"));                     // (tools/direct_check.py switches it between two runs of one process)
   const bool deep = env_not0(getenv("FGX_DEEP"));
+  const char* const deep_wide_env = getenv("FGX_DEEP_WIDE");
+  const bool deep_wide = deep_wide_env && deep_wide_env[0] && deep_wide_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the wide kernels behind the streaming ones (simplex_wide.inc)
   const uint32_t seg_bytes = env_in(fgx_knob("FGX_SEG_BYTES"), 4096, 32768, 11776) & ~63u;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
   const uint32_t wave_bytes = env_in(fgx_knob("FGX_WAVE_BYTES"), 1024, 22016, 0) & ~15u;     // tuning knobs (0: the FastPath's own value)
   const uint32_t lds_tile_large = env_in(fgx_knob("FGX_LDS_TILE_LARGE"), 16384, 163840, 0) & ~15u;
@@ -3147,7 +3150,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
-    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
+    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
     fp.d_offsets.reserve(((size_t)n_slots + 1) * 8);
@@ -3578,6 +3581,56 @@ struct Batch {
     sync();
     return n_left;
   }
+  // One pass of the wide kernels (simplex_wide.inc) over what the streaming kernels left; returns how many families it handed on (to `out`).
+  uint32_t wide_pass(const uint32_t* list, uint32_t n_list, uint32_t* out) {
+    fp.d_deep_sizes.reserve((size_t)n_list * 8 + 64); fp.d_deep_row0.reserve((size_t)n_list * 8 + 64);
+    hip_check(hipMemsetAsync(cnt(MISC_N_DEEP), 0, 4, s), "memset");   // (first: the largest family; then, cleared again, the families handed on)
+    FGX_LAUNCH(k_wide_sizes, dim3((n_list + 255) / 256), dim3(256), 0, s, list, n_list, d_grp_first, fp.d_deep_sizes.as<uint64_t>(), cnt(MISC_N_DEEP));
+    scan_u64(fp.d_deep_sizes.as<uint64_t>(), fp.d_deep_row0.as<uint64_t>(), n_list, "scan of the wide families' records");
+    uint64_t lastr[2] = {0, 0};
+    uint32_t n_max = 0;
+    hip_check(hipMemcpyAsync(&n_max, cnt(MISC_N_DEEP), 4, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&lastr[0], fp.d_deep_row0.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&lastr[1], fp.d_deep_sizes.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    const uint64_t n_rows = lastr[0] + lastr[1];
+    if (n_rows > (uint64_t)n_rec) throw std::runtime_error("device pipeline: " + std::to_string(n_rows) + " rows for the wide kernels, more than the batch has records");
+    WideParams W;
+    memset(&W, 0, sizeof(W));
+    W.n_rows = (n_rows + 7) & ~7ull;
+    W.lds_recs = std::min<uint32_t>(WIDE_MAX, (n_max + 63u) & ~63u);
+    if (W.lds_recs == 0) W.lds_recs = 64;
+    fp.d_deep_rows.reserve((size_t)n_rows * sizeof(DeepRow) + 64); fp.d_deep_fams.reserve((size_t)n_list * sizeof(DeepFam) + 64);
+    fp.d_wide_scratch.reserve((size_t)W.n_rows * WIDE_REC_BYTES + 64);
+    fp.d_wide_pass.reserve((size_t)n_list * 8 + 64); fp.d_wide_pass0.reserve((size_t)n_list * 8 + 64);
+    hip_check(hipMemsetAsync(cnt(MISC_N_DEEP), 0, 4, s), "memset");
+    hip_check(hipMemsetAsync(fp.d_wide_pass.p, 0, (size_t)n_list * 8, s), "memset");
+    W.list = list; W.n_list = n_list; W.row0 = fp.d_deep_row0.as<uint64_t>();
+    W.scratch = fp.d_wide_scratch.as<uint8_t>();
+    W.rows = fp.d_deep_rows.as<DeepRow>(); W.fams = fp.d_deep_fams.as<DeepFam>(); W.out_list = out; W.n_out = cnt(MISC_N_DEEP);
+    W.passes = fp.d_wide_pass.as<uint64_t>(); W.pass0 = fp.d_wide_pass0.as<uint64_t>();
+    FastParams PD = P;
+    PD.group_list = nullptr;
+    const uint32_t lds = W.lds_recs * WIDE_LDS_PER_REC;
+    FGX_LDS_ATTR((int)WIDE_LDS_BYTES, k_wide_parse);
+    FGX_LAUNCH(k_wide_parse, dim3(n_list), dim3(WIDE_NT), lds, s, PD, W);
+    scan_u64(fp.d_wide_pass.as<uint64_t>(), fp.d_wide_pass0.as<uint64_t>(), n_list, "scan of the wide families' passes");
+    uint64_t lastp[2] = {0, 0};
+    uint32_t n_left = 0;
+    hip_check(hipMemcpyAsync(&lastp[0], fp.d_wide_pass0.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&lastp[1], fp.d_wide_pass.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&n_left, cnt(MISC_N_DEEP), 4, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    const uint64_t n_items = lastp[0] + lastp[1];
+    // (a taken family has at most two ends of at most 65 535 columns: 2 048 passes)
+    if (n_items > (uint64_t)n_list * 2048ull) throw std::runtime_error("device pipeline: " + std::to_string(n_items) + " column passes for " + std::to_string(n_list) + " wide families");
+    W.n_items = (uint32_t)n_items;
+    fp.d_wide_depth.reserve((size_t)n_items * sizeof(uint2) + 64);
+    W.item_depth = fp.d_wide_depth.as<uint2>();
+    if (n_items) FGX_LAUNCH(k_wide_cols, dim3((W.n_items + 3) / 4), dim3(256), 0, s, PD, W);
+    FGX_LAUNCH(k_wide_finish, dim3((n_list + 3) / 4), dim3(256), 0, s, PD, W);
+    return n_left;
+  }
   void deep_families() {
     if (!duplex && !codec) {
       if (split_counts_seen && fp.last_routed == 0) n_big = h_big_seen;   // (no kernel after the split stages has run: what their last synchronisation read is final)
@@ -3614,6 +3667,17 @@ struct Batch {
       }
     }
     fp.last_deep_families = meth_dev ? n_big : n_big - n_left;
+    // FGX_DEEP_WIDE=1: what those builds left — more records than they hold, an end of more than 255 reads — through the wide kernels; the rest goes on
+    if (sw.deep_wide && n_left && !meth_dev && !duplex && !codec) {
+      const bool in_out2 = big_list == fp.d_deep_out2.as<uint32_t>();
+      DevBuf& ob = in_out2 ? fp.d_deep_out : fp.d_deep_out2;
+      ob.reserve((size_t)n_left * 4 + 64);
+      const uint32_t* const in_list = in_out2 ? fp.d_deep_out2.as<uint32_t>() : fp.d_deep_out.as<uint32_t>();   // (reserve may have moved the other buffer, not this one)
+      const uint32_t n_after = wide_pass(in_list, n_left, ob.as<uint32_t>());
+      fp.last_wide_families = n_left - n_after;
+      n_left = n_after;
+      big_list = ob.as<uint32_t>();
+    }
     if (meth_dev) fp.last_meth_device = n_grp;
     n_big = meth_dev ? 0u : n_left;   // (what is not the kernels' shape: k_family)
   }
