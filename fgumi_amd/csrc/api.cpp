@@ -1508,6 +1508,16 @@ void fgx_debug_last_split_builds(const fgx_caller* c, uint64_t* out4) {
   out4[0] = out4[1] = out4[2] = out4[3] = 0;
   if (c && c->fast) { const FastPath& f = c->fast->fp; out4[0] = f.last_packed_families; out4[1] = f.last_classic_families; out4[2] = f.last_split_build; out4[3] = f.last_first_stage_retries; }
 }
+// the LDS slice of a wavefront in the first k_split_cols launch of a batch of `mean_records` records per family, from the constants the driver
+// uses (s2_first_slice_bytes): out4[0] the slice, [1] the room behind the tile of a family of mean_records records, [2] bytes of a FullItem, [3] bytes of
+// the descriptor of a column the packed pass does not answer itself
+void fgx_debug_split_first_slice(double mean_records, int packed, uint32_t* out4) {
+  if (!out4) return;
+  out4[0] = s2_first_slice_bytes(mean_records, packed != 0);
+  out4[1] = out4[0] - s2_tile_bytes(mean_records);
+  out4[2] = (uint32_t)sizeof(FullItem);
+  out4[3] = S2_FLAG_DESC_BYTES;
+}
 // the packed build's families of the last device batch by row loop: out2[0] clean (every raw quality at or above --min-input-base-quality:
 // the loop reads no quality), out2[1] general
 void fgx_debug_last_packed_rows(const fgx_caller* c, uint64_t* out2) {

@@ -1,5 +1,6 @@
 // fastpath.h — declarations for the device-resident simplex pipeline (fastpath.hip).
 #pragma once
+#include <algorithm>
 #include "engine.h"
 
 namespace fgx {
@@ -59,6 +60,22 @@ struct FullItem {           // a column (or UMI character) whose call needs the 
   uint32_t chains;          // 0, or the one-hot BAM codes of chains 1 | 2 << 4 | 3 << 8 (0 = chain not opened); every other base reads chain R
 };
 constexpr int N_LISTS = 1024;
+// LDS slice of a wavefront in the FIRST k_split_cols launch of a batch (choose_split_build, fastpath.hip): the MEAN family's tile — rows of
+// 160 + 80 bytes, 16 bytes of slack — and room behind it: in the packed build for the 8-byte descriptors of the columns the pass does not answer
+// itself and the FullItems of those that need k_call_full (56 bytes per such column, ~14 flagged columns and 3.3 items per depth-8 family of
+// `simulate` data); at least the slice of a 16-record family.  A family whose flagged columns and items do not fit takes the next launch.
+// The packed build's 5632 bytes — 1776 of room at depth 8 — are seven workgroups of four wavefronts in a CU's 160 KB.  5024 bytes (1168 of
+// room: an eighth workgroup, which the packed kernel's registers allow) were measured and NOT taken — profiles/cols_scalar_state.md: 0.29 ms
+// of 26.4 less per depth-8 step, but 18 families of 5 M sent to the second launch where there were none, and a long-tail batch, whose families of
+// 20 and 21 records then miss the first slice, 8 ms of 68 slower.
+constexpr uint32_t S2_ROW_BYTES = 240, S2_TILE_SLACK = 16, S2_ROOM_PACKED = 1680, S2_ROOM_CLASSIC = 400, S2_SLICE16_PACKED = 5632, S2_SLICE16_CLASSIC = 4352,
+                   S2_FLAG_DESC_BYTES = 8;
+inline uint32_t s2_tile_bytes(double mean_recs) { return (uint32_t)(mean_recs + 0.999) * S2_ROW_BYTES + S2_TILE_SLACK; }
+inline uint32_t s2_first_slice_bytes(double mean_recs, bool packed) {
+  const uint32_t floor16 = packed ? S2_SLICE16_PACKED : S2_SLICE16_CLASSIC;
+  const uint32_t mean_need = s2_tile_bytes(mean_recs) + (packed ? S2_ROOM_PACKED : S2_ROOM_CLASSIC);
+  return mean_need > floor16 ? std::min<uint32_t>((mean_need + 15u) & ~15u, 17408u) : floor16;
+}
 // FullItem.chains with this bit set: the column did not stay with one base — `ll` holds its observations instead of chains,
 // 16-bit each (4-bit code in consensus orientation << 8 | quality), chains & 0xFF of them in file order (at most 16);
 // k_call_full accumulates them with the four-lane Kahan loop (base_builder.rs:836-868) and calls the column

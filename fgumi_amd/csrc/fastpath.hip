@@ -3046,10 +3046,8 @@ SplitBuild choose_split_build(const SplitFam* sample, uint32_t n_sample, double 
   // as a whole (depth 12: every family took two launches, 32 ms per 1 M families).
   // (round 5: the packed pass sends every column it does not answer itself to k_call_full — also the one-base columns of too few
   // observations, which run_cols's gates answer — and keeps an 8-byte descriptor per such column at the top of the slice: 56 bytes per
-  // column, ~14 columns per depth-8 family of `simulate` data; 5632 bytes x 4 wavefronts still leave a CU six workgroups)
-  uint32_t bytes0 = B.packed ? 5632 : 4352;
-  const uint32_t mean_need = (uint32_t)(mean_recs + 0.999) * 240u + 16u + (B.packed ? 1680u : 400u);
-  if (mean_need > bytes0) bytes0 = std::min<uint32_t>((mean_need + 15u) & ~15u, 17408u);
+  // column, ~14 columns per depth-8 family of `simulate` data: the room behind the tile is S2_ROOM_PACKED, fastpath.h)
+  uint32_t bytes0 = s2_first_slice_bytes(mean_recs, B.packed);
   if (ps.s2_bytes) bytes0 = ps.s2_bytes;
   const uint32_t wpb0 = ps.s2_wpb ? ps.s2_wpb : (bytes0 <= 6528u ? 4u : bytes0 <= 13056u ? 2u : 1u);
   // rows of 160 + 80 bytes (reads up to 160 bases) have their own build: member rows at immediate offsets in the column loop.  Every slice

@@ -33,7 +33,7 @@
 #define FGX_S2_OCC 6
 #endif
 #ifndef FGX_S2_OCC_PACKED
-#define FGX_S2_OCC_PACKED 7   /* the packed build: 71 VGPRs, 5632-byte slices and ~100 bytes of tables — seven workgroups of four wavefronts in a CU's 160 KB */
+#define FGX_S2_OCC_PACKED 7   /* the packed build: 46 VGPRs (eight wavefronts per SIMD by registers), 5632-byte slices and 368 bytes of tables — seven workgroups of four wavefronts in a CU's 160 KB; at a bound of 8 the compiler caps the kernel at 78 scalar registers and its uniforms spill again */
 #endif
 #ifndef FGX_S2_PAIRS
 #define FGX_S2_PAIRS 256   /* rows of the {correct, error} table: 256 = indexed by the raw quality byte (no clamp in the loop) */
@@ -690,6 +690,21 @@ template <int COLS> struct S2SharedOf {
 #endif
 };
 typedef uint32_t s2_u32x4 __attribute__((ext_vector_type(4)));
+// The kernel's FastParams read AGAIN from the kernarg segment, at the place of use (the packed build only).  The compiler loads every field of the
+// by-value argument it needs anywhere in one go and keeps them live: ~40 scalar registers of pointers that the record and result phases use
+// once each, which is what pushed the family's own uniforms into spill lanes (v_writelane / v_readlane on the vector pipe, the one this kernel
+// is short of).  A scalar load where the field is used costs the scalar cache's latency, not a vector slot.  The pin keeps the compiler from
+// merging the reads back into the one at the top.  k_split_cols's first argument IS the FastParams: offset 0 of the segment.
+template <bool AGAIN> struct S2Args { static __device__ __forceinline__ const FastParams& of(const FastParams& P) { return P; } };
+#if !defined(FGX_WAVEMU)
+template <> struct S2Args<true> {
+  static __device__ __forceinline__ const FGX_CONST_AS FastParams& of(const FastParams&) {
+    const FGX_CONST_AS FastParams* k = (const FGX_CONST_AS FastParams*)__builtin_amdgcn_kernarg_segment_ptr();
+    FGX_PIN("+s"(k));
+    return *k;
+  }
+};
+#endif
 // ONE family through the column kernel (round 6: a function of its own; FUSED — the tables are in LDS already, nothing of the workgroup is waited
 // for — served the experiment k_split_fused, a wavefront that parsed a round of records and then decided the round's families: profiles/r06_experiments.md).
 template <int QS_T, int SS_T, int DIRECT, int COLS, bool FUSED>   // row strides of the quality / sequence tiles (0, 0: the family's own, from its descriptor); DIRECT 1: the
@@ -706,6 +721,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   constexpr uint32_t IMG_V = TINY ? 0u : (uint32_t)((FGX_S2_F32 ? S2_HEAD_BYTES : (uint32_t)sizeof(S2Lds)) / 16);   // (f32 sums: the gate tables and the f32 pairs only)
   const unsigned long long below = (1ull << lane) - 1ull;
   (void)sT; (void)IMG_V; (void)tiny_w; (void)im; (void)below;
+  typedef S2Args<COLS == 1 && !FUSED> KA;     // KA::of(P).field: the packed build reads the field from the kernarg segment right there
 
   const uint4 fd = P.fam_desc[g];
   const u32x4 f0 = ((const u32x4*)&P.split_fam[g])[0], f1 = ((const u32x4*)&P.split_fam[g])[1];
@@ -717,7 +733,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   // what this wavefront leaves for k_split_finish: one 32-byte result (status 0 = the family is another kernel's)
   auto leave = [&](uint32_t status, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t w5, uint32_t w6) {
     if (lane == 0) {
-      u32x4* o = (u32x4*)&P.split_out[g];
+      u32x4* o = (u32x4*)&KA::of(P).split_out[g];
       const u32x4 a = {status | w1, w2, w3, w4}, b = {w5, w6, 0u, 0u};
       o[0] = a; o[1] = b;
     }
@@ -733,9 +749,9 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   };
   if (!bail && n < P.min_reads) { leave(2u, 0, n << 24, 0, 0, 0, 0); if (DIRECT) dir_tables(0, 0, 0); bail = true; }   // simplex.rs:673-683: counted by k_split_finish
   // not this kernel's: k_simplex_wave2 decides (and hands on what is not its shape either)
-  auto to_route = [&]() { leave(0u, 0, 0, 0, 0, 0, 0); if (lane == 0) { uint32_t k = atomicAdd(P.n_route, 1u); P.route[k] = g; } };
+  auto to_route = [&]() { leave(0u, 0, 0, 0, 0, 0, 0); if (lane == 0) { uint32_t k = atomicAdd(KA::of(P).n_route, 1u); KA::of(P).route[k] = g; } };
   // fits the shape but not this launch's LDS slice: the next launch of this kernel (bigger slices)
-  auto to_retry = [&]() { if (!P.retry) { to_route(); return; } leave(0u, 0, 0, 0, 0, 0, 0); if (lane == 0) { uint32_t k = atomicAdd(P.n_retry, 1u); P.retry[k] = g; } };
+  auto to_retry = [&]() { if (!KA::of(P).retry) { to_route(); return; } leave(0u, 0, 0, 0, 0, 0, 0); if (lane == 0) { uint32_t k = atomicAdd(KA::of(P).n_retry, 1u); KA::of(P).retry[k] = g; } };
   // SplitFam: flags | need_bytes | qs, ss | n, m_a, m_b, type_a || rev_a, rev_b, rx_len, rx_all | len_a, len_b | inv_cpr | qc, sc
   const uint32_t f_flags = uni(f0.x), need = uni(f0.y);
   const uint32_t QS = QS_T ? (uint32_t)QS_T : uni(f0.z & 0xFFFF), SS = SS_T ? (uint32_t)SS_T : uni(f0.z >> 16);
@@ -747,7 +763,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     const bool mine = s2_packed_shape(m_a, m_b, len_a, len_b, P.s2_nsafe) == (COLS == 1);
     if (!bail && !mine) { if (COLS == 1 && !P.s2_partner) to_retry(); bail = true; }   // (no partner launch — the batch's sample showed this shape only —: the next launch takes it)
   }
-  if (!bail && n > 64u && P.big) { leave(0u, 0, 0, 0, 0, 0, 0); if (lane == 0) { uint32_t k = atomicAdd(P.n_big, 1u); P.big[k] = g; } bail = true; }   // k_family's, directly
+  if (!bail && n > 64u && KA::of(P).big) { leave(0u, 0, 0, 0, 0, 0, 0); if (lane == 0) { uint32_t k = atomicAdd(KA::of(P).n_big, 1u); KA::of(P).big[k] = g; } bail = true; }   // k_family's, directly
   if (!bail && (!(f_flags & 1u) || n > 64u)) { to_route(); bail = true; }
   if (!bail && QS_T && ((f0.z & 0xFFFF) != (uint32_t)QS_T || (f0.z >> 16) != (uint32_t)SS_T)) { to_retry(); bail = true; }   // other strides: the generic build
   const uint32_t ibase = need + 16;
@@ -1048,10 +1064,17 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   // ---- 6. consensus columns -------------------------------------------------------------------------------------------------------
   const DeviceTables* T = P.T;
   const uint64_t col_base = uniform_u64(col_base_early);
-  uint8_t* const fam_code = P.col_code + col_base;
-  uint8_t* const fam_qual = P.col_qual + col_base;
-  uint16_t* const fam_depth = P.col_depth + col_base;
-  uint16_t* const fam_err = P.col_err + col_base;
+  // the family's part of the four scratch planes (the packed build works them out where it writes them — planes(), from the kernarg segment, see
+  // S2Args —: ten scalar registers that were live from here to the end)
+  uint8_t* const fam_code = COLS == 1 ? nullptr : P.col_code + col_base;
+  uint8_t* const fam_qual = COLS == 1 ? nullptr : P.col_qual + col_base;
+  uint16_t* const fam_depth = COLS == 1 ? nullptr : P.col_depth + col_base;
+  uint16_t* const fam_err = COLS == 1 ? nullptr : P.col_err + col_base;
+  struct Planes { uint8_t* code; uint8_t* qual; uint16_t* depth; uint16_t* err; };
+  auto planes = [&]() -> Planes {
+    if constexpr (COLS != 1) return Planes{fam_code, fam_qual, fam_depth, fam_err};
+    else { const auto& K = KA::of(P); return Planes{K.col_code + col_base, K.col_qual + col_base, K.col_depth + col_base, K.col_err + col_base}; }
+  };
   const uint8_t* pairs = nullptr;
   if constexpr (!TINY) {
 #if FGX_S2_F32
@@ -1062,6 +1085,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   }
   // a single-read end: LUT keyed by the unclamped quality (:1677-1708)
   auto single_end = [&](unsigned long long members, uint32_t Lc, uint32_t coff) {
+    const Planes PL = planes();
     const uint32_t r = (uint32_t)__builtin_ctzll(members);
     const uint32_t s_r = rlane(my_s, r), q_r = rlane(my_q, r), L_r = rlane(l_seq, r);
     const bool rv_r = (rlane(bits, r) & 4u) != 0;
@@ -1076,7 +1100,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
       if constexpr (DIRECT != 0) { (void)coff; }
       else {
         const uint32_t oc = coff + p;
-        fam_code[oc] = ob; fam_qual[oc] = oq; fam_depth[oc] = (uint16_t)(code != 15 ? 1 : 0); fam_err[oc] = 0;
+        PL.code[oc] = ob; PL.qual[oc] = oq; PL.depth[oc] = (uint16_t)(code != 15 ? 1 : 0); PL.err[oc] = 0;
       }
     }
   };
@@ -1346,7 +1370,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     const uint32_t ga = cnt_a ? (len_a + 7u) >> 3 : 0u, gb = cnt_b ? (len_b + 7u) >> 3 : 0u;      // lanes of end A, of end B
     const bool dbg = (P.s2_packed & 2u) != 0;
     if (!(P.s2_packed && m >= nsafe && m <= S2_PACKED_MAX_ROWS && P.min_reads <= nsafe && min_bq <= 128u && ((QS & 7u) | (SS & 3u)) == 0u && ga + gb <= 64u &&
-          S0 + s2_mul24(n, SS) < 65536u && lc_a + lc_b < 65536u)) {
+          S0 + n * SS < 65536u && lc_a + lc_b < 65536u)) {       // (wave-uniform operands: the scalar multiply — s2_mul24's result is a vector register, and a branch on it a divergent one)
       if (dbg && lane == 0) atomicAdd(&g_s2_dbg[42], 1u);
       return false;
     }
@@ -1396,7 +1420,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     const uint32_t list = (P.lds_wave_bytes - 8u * T) & ~7u;
     // (room: the descriptors of the flagged columns at the top of the slice; the items — of the columns that turn out to need one, below — grow
     // from ibase towards them and are checked as they are made)
-    if (T && (8u * T + 8u > P.lds_wave_bytes || ibase + s2_mul24(icnt, (uint32_t)sizeof(FullItem)) > list)) {
+    if (T && (8u * T + 8u > P.lds_wave_bytes || ibase + icnt * (uint32_t)sizeof(FullItem) > list)) {
       if (dbg && lane == 0) atomicAdd(&g_s2_dbg[3], 1u);
       gone = true; return true;
     }
@@ -1408,11 +1432,12 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     //      entries.)  32-bit offsets from the family's first scratch column: scalar base + lane offset addressing.
     (void)full2; (void)lo_s;
     if (hi_s > lo_s) {
+      const Planes PL = planes();
       const uint2 cv = make_uint2(code2[0], code2[1]), qv = make_uint2(qual2[0], qual2[1]);
       const u32x4 dv = {dep4[0], dep4[1], dep4[2], dep4[3]}, zv = {0u, 0u, 0u, 0u};
       const uint32_t o1 = oc0, o2 = 2u * oc0;
-      __builtin_memcpy(fam_code + o1, &cv, 8); __builtin_memcpy(fam_qual + o1, &qv, 8);
-      __builtin_memcpy((uint8_t*)fam_depth + o2, &dv, 16); __builtin_memcpy((uint8_t*)fam_err + o2, &zv, 16);
+      __builtin_memcpy(PL.code + o1, &cv, 8); __builtin_memcpy(PL.qual + o1, &qv, 8);
+      __builtin_memcpy((uint8_t*)PL.depth + o2, &dv, 16); __builtin_memcpy((uint8_t*)PL.err + o2, &zv, 16);
     }
     PH(12)
     if (T) {
@@ -1435,7 +1460,9 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
       // OTHER column gets a k_call_full item: its slot = the number of such columns before it (round 6; round 5 wrote an item for every
       // flagged column and turned those of the answered ones into continuation items afterwards: 7.3 items per family went to k_call_full
       // where 3.3 were needed).
-      const uint8_t* const t2g = ((const S2Image*)P.s2_image)->t2;
+      const auto& K6 = KA::of(P);                                                                           // (one read of the segment for the planes and the table)
+      const Planes PL = {K6.col_code + col_base, K6.col_qual + col_base, K6.col_depth + col_base, K6.col_err + col_base};
+      const uint8_t* const t2g = ((const S2Image*)K6.s2_image)->t2;
       const uint32_t rp_sh = m <= 8u ? 3u : m <= 16u ? 4u : 5u, rows_per = 1u << rp_sh, cps = 64u >> rp_sh;   // (8 x 8, 4 x 16 or — ends of 17 .. 31 rows: two items per column — 2 x 32)
       const uint32_t per_cold = (m + 15u) >> 4;
       const uint32_t ce = lane >> rp_sh, j = lane & (rows_per - 1u), lane0 = lane & ~(rows_per - 1u);
@@ -1470,7 +1497,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
         const unsigned long long needm = __ballot(need && j == 0u);
         const uint32_t n_need = per_cold * (uint32_t)__popcll(needm);                                       // items: ceil(m / 16) consecutive ones per column
         if (per_cold > 1u && needm) multi_items = true;
-        if (ibase + s2_mul24(icnt + n_need, (uint32_t)sizeof(FullItem)) > list) {                            // no room for this step's items: the next launch (larger slices)
+        if (ibase + (icnt + n_need) * (uint32_t)sizeof(FullItem) > list) {                                    // no room for this step's items: the next launch (larger slices)
           if (dbg && lane == 0) atomicAdd(&g_s2_dbg[3], 1u);
           gone = true; return true;
         }
@@ -1485,8 +1512,8 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
           if (nobs < P.min_reads) { ob = 15; oq = 0; }
           else if (tq < P.min_cons_bq) { ob = 15; oq = FGX_MIN_PHRED; }
           else { ob = c1; oq = tq; }
-          fam_code[oc_l] = (uint8_t)ob; fam_qual[oc_l] = (uint8_t)oq;
-          *(uint16_t*)((uint8_t*)fam_depth + 2u * oc_l) = (uint16_t)nobs; *(uint16_t*)((uint8_t*)fam_err + 2u * oc_l) = (uint16_t)0;
+          PL.code[oc_l] = (uint8_t)ob; PL.qual[oc_l] = (uint8_t)oq;
+          *(uint16_t*)((uint8_t*)PL.depth + 2u * oc_l) = (uint16_t)nobs; *(uint16_t*)((uint8_t*)PL.err + 2u * oc_l) = (uint16_t)0;
         }
         icnt = uni(icnt + n_need);
       }
@@ -1495,6 +1522,13 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     if (dbg && lane == 0) { atomicAdd(&g_s2_dbg[1], 1u); atomicAdd(&g_s2_dbg[2], T); }
     return true;
   };
+  // (packed build) the family's result for k_split_finish — phase 7 — goes out HERE, before the column pass: everything in it is known, and the
+  // thirteen uniforms it is made of otherwise wait in spill lanes across the pass.  A family that leaves after all (no room in the slice, a full
+  // list) overwrites it through the same lane: stores of one wavefront to one address reach memory in program order.
+  if constexpr (COLS == 1) {
+    leave(__any(dirty_v != 0u) ? 0x81u : 0xC1u, (ne << 8) | (type_a << 16) | (fk_a << 24), fk_b | (surv_a << 8) | (surv_b << 16) | (n << 24), lc_a | (lc_b << 16), rej, ov_agree, ov_dis);
+    if (lane == 0) ((uint32_t*)&KA::of(P).split_out[g])[6] = ov_corr;
+  }
   {
     const bool multi_a = ne >= 1u && surv_a >= 2u, multi_b = ne == 2u && surv_b >= 2u;
     if constexpr (DIRECT != 0) {
@@ -1504,16 +1538,27 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
       if (ne >= 1u && surv_a == 1u) single_end(mem_a, lc_a, offA);
       if (ne == 2u && surv_b == 1u) single_end(mem_b, lc_b, offB);
     }
-    // one run over both ends when they have equally many rows, else a run per end (ONE copy of the loop in the code)
+    // one run over both ends when they have equally many rows, else a run per end (the classic builds: ONE copy of the loop in the code)
     const bool both = multi_a && multi_b && m_a == m_b;
     const uint32_t nruns = both ? 1u : (multi_a ? 1u : 0u) + (multi_b ? 1u : 0u);
+    if constexpr (COLS == 1) {
+      // the packed pass WITHOUT the loop: the second run — ends of unequal row counts, rare — is a copy of its own behind the first.  A loop around
+      // a body with divergent branches is structurized as a whole: every `return` of the pass became a lane mask carried round the loop in a pair
+      // of scalar registers, eight pairs in all, and the family's uniforms went to spill lanes to make room for them.
+      // (false: a shape the test at the top let through and the pass refuses — the next launch, run_cols)
+      if (nruns != 0u) {
+        const bool run_a = both || multi_a;
+        if (!run_cols_packed(run_a ? lc_a : 0u, (both || !run_a) ? lc_b : 0u, run_a ? m_a : m_b, nruns == 1u)) gone = true;
+      }
+      if (nruns == 2u && !gone) { if (!run_cols_packed(0u, lc_b, m_b, true)) gone = true; }
+    } else {
 #pragma unroll 1
-    for (uint32_t ri = 0; ri < nruns && !gone; ri++) {
-      const bool first_is_a = both || multi_a;
-      const bool run_a = ri == 0 && first_is_a, run_b = both || !run_a;
-      const uint32_t rc_a = run_a ? lc_a : 0u, rc_b = run_b ? lc_b : 0u, rc_m = run_a ? m_a : m_b;
-      if constexpr (COLS == 1) { if (!run_cols_packed(rc_a, rc_b, rc_m, ri + 1 == nruns)) gone = true; }   // (a shape the test at the top let through and the pass refuses: the next launch, run_cols)
-      else run_cols(rc_a, rc_b, rc_m);
+      for (uint32_t ri = 0; ri < nruns && !gone; ri++) {
+        const bool first_is_a = both || multi_a;
+        const bool run_a = ri == 0 && first_is_a, run_b = both || !run_a;
+        const uint32_t rc_a = run_a ? lc_a : 0u, rc_b = run_b ? lc_b : 0u, rc_m = run_a ? m_a : m_b;
+        run_cols(rc_a, rc_b, rc_m);
+      }
     }
     // no room behind the tile for the columns that wait for k_call_full: the next launch of this kernel has larger slices (a family of a noisy
     // library); the last one hands the family to k_simplex_wave2.
@@ -1526,8 +1571,8 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   // reserve room for this family's items (the result is looked at after the store below)
   uint32_t ires = 0;
   if (ires_asked) ires = ires_early;
-  else if (icnt && lane == 0) ires = atomicAdd(&P.full_count[my_list], icnt);
-  {
+  else if (icnt && lane == 0) ires = atomicAdd(&KA::of(P).full_count[my_list], icnt);
+  if constexpr (COLS != 1) {
     leave(COLS == 1 ? (__any(dirty_v != 0u) ? 0x81u : 0xC1u) : 1u, (ne << 8) | (type_a << 16) | (fk_a << 24), fk_b | (surv_a << 8) | (surv_b << 16) | (n << 24), lc_a | (lc_b << 16), rej, ov_agree, ov_dis);
     if (lane == 0) ((uint32_t*)&P.split_out[g])[6] = ov_corr;
   }
@@ -1548,53 +1593,56 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     };
     if (ne >= 1u) tail(RA, sm & 0xFFFFu);
     if (ne == 2u) tail(RB, sm >> 16);
-    if (lane == 0) ((uint32_t*)&P.split_out[g])[7] = (mx & 0xFFu) | ((mn & 0xFFu) << 8) | (((mx >> 16) & 0xFFu) << 16) | (((mn >> 16) & 0xFFu) << 24);   // cD / cM of both records
+    if (lane == 0) ((uint32_t*)&KA::of(P).split_out[g])[7] = (mx & 0xFFu) | ((mn & 0xFFu) << 8) | (((mx >> 16) & 0xFFu) << 16) | (((mn >> 16) & 0xFFu) << 24);   // cD / cM of both records
     dir_tables(type_a == 0u ? RA.size : 0u, type_a == 0u ? 0u : RA.size, RB.size);
   }
   if (icnt) {   // the family's items: LDS -> the reserved range, 16 bytes per lane and step; a range that crosses the end of its list
                 // continues in the next list (one more, synchronous, reservation — rare)
     wave_sync();
+    const auto& K7 = KA::of(P);
+    const uint32_t full_cap = K7.full_cap;
+    FullItem* const full_items = K7.full_items;
     uint32_t base = uni(ires), l = my_list, done = 0, tries = 0;
     bool overflow = false;
     if (multi_items) {
       // a column of several consecutive items must not be cut at the end of a list: the reservation that does not hold the WHOLE family is
       // filled with continuation items (k_call_full skips them) and the family's items go to the next list that holds them all
       for (;;) {
-        if (base < P.full_cap && icnt <= P.full_cap - base) {
+        if (base < full_cap && icnt <= full_cap - base) {
           const uint4* src = (const uint4*)(W + ibase);
-          uint4* dst = (uint4*)(P.full_items + ((size_t)l * P.full_cap + base));
+          uint4* dst = (uint4*)(full_items + ((size_t)l * full_cap + base));
           for (uint32_t c = lane; c < 3 * icnt; c += 64) dst[c] = src[c];
           break;
         }
-        if (base < P.full_cap) {
-          FullItem* pad = P.full_items + ((size_t)l * P.full_cap + base);
-          for (uint32_t c = lane; c < P.full_cap - base; c += 64) { pad[c].dest = 0; pad[c].obs = 0; pad[c].chains = FULL_ITEM_CONT; }
+        if (base < full_cap) {
+          FullItem* pad = full_items + ((size_t)l * full_cap + base);
+          for (uint32_t c = lane; c < full_cap - base; c += 64) { pad[c].dest = 0; pad[c].obs = 0; pad[c].chains = FULL_ITEM_CONT; }
         }
         if (++tries >= N_LISTS) { overflow = true; break; }
         l = (l + 1) & (N_LISTS - 1);
         uint32_t b2 = 0;
-        if (lane == 0) b2 = atomicAdd(&P.full_count[l], icnt);
+        if (lane == 0) b2 = atomicAdd(&KA::of(P).full_count[l], icnt);
         base = uni(b2);
       }
     } else
     for (;;) {
       const uint32_t rem = icnt - done;
-      const uint32_t fit = base < P.full_cap ? (rem < P.full_cap - base ? rem : P.full_cap - base) : 0u;
+      const uint32_t fit = base < full_cap ? (rem < full_cap - base ? rem : full_cap - base) : 0u;
       const uint4* src = (const uint4*)(W + ibase) + 3 * done;
-      uint4* dst = (uint4*)(P.full_items + ((size_t)l * P.full_cap + base));
+      uint4* dst = (uint4*)(full_items + ((size_t)l * full_cap + base));
       for (uint32_t c = lane; c < 3 * fit; c += 64) dst[c] = src[c];
       done += fit;
       if (done == icnt) break;
       if (++tries >= N_LISTS) { overflow = true; break; }
       l = (l + 1) & (N_LISTS - 1);
       uint32_t b2 = 0;
-      if (lane == 0) b2 = atomicAdd(&P.full_count[l], icnt - done);
+      if (lane == 0) b2 = atomicAdd(&KA::of(P).full_count[l], icnt - done);
       base = uni(b2);
     }
     if (overflow) {   // every list is full: the general path redoes the family (its result is withdrawn: no records, nothing counted)
       leave(3u, 0, 0, 0, 0, 0, 0);
       if (DIRECT) dir_tables(0, 0, 0);                         // (its records are in place already: the host takes the batch through the merge)
-      if (lane == 0) { uint32_t kk = atomicAdd(P.n_deferred, 1u); P.deferred[kk] = g; }
+      if (lane == 0) { uint32_t kk = atomicAdd(KA::of(P).n_deferred, 1u); KA::of(P).deferred[kk] = g; }
       return;
     }
   }
