@@ -52,6 +52,7 @@
 #include "fastpath.h"
 #include "gate_core.h"
 #include "packed_core.h"
+#include "record_core.h"
 
 // The device-only spellings behind macros, so that tests/wavemu (a wave-level host emulator of the wavefront kernels) can compile this
 // file for the host: dynamic LDS, and the inline assembly — scheduling pins for the device compiler ("+v" / "s" constraints mean nothing on a CPU) and
@@ -349,6 +350,10 @@ __device__ __forceinline__ unsigned long long ld64u(const uint8_t* W, uint32_t o
   return (unsigned long long)__builtin_amdgcn_alignbyte(w1, w0, sh) | ((unsigned long long)__builtin_amdgcn_alignbyte(w2, w1, sh) << 32);
 #endif
 }
+// unaligned reads of global memory (a record's fields lie at any byte offset).  record_writers.inc keeps a pair of its own with the same bodies (gld32u / gld64u):
+// calling these from the writers instead changes k_emit's register allocation (profiles/record_core.md)
+__device__ __forceinline__ uint32_t gld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ unsigned long long gld64(const uint8_t* p) { unsigned long long v; __builtin_memcpy(&v, p, 8); return v; }
 // offset of the first NUL in W[o, o+n), 8 bytes per step; -1 if none
 __device__ __forceinline__ int find_nul64(const uint8_t* W, uint32_t o, uint32_t n) {
   for (uint32_t i = 0; i < n; i += 8) {
@@ -362,10 +367,7 @@ __device__ __forceinline__ int find_nul64(const uint8_t* W, uint32_t o, uint32_t
 // Aux walk of one record per lane, in LDS (tags.rs:13-34): first occurrence of MC / <tag> / RX / <cell tag>.
 // The walk keeps its state in integer lanes (bit 0 MC, 1 <tag>, 2 RX, 3 <cell tag>) and picks with selects: boolean state
 // would live in scalar lane masks, and every `if` on it costs scalar mask instructions for all 64 records.
-struct AuxTags {
-  uint32_t got, oddw;                          // keys found with a Z value ; <tag> / RX / <cell tag> values longer than 255 bytes
-  uint32_t pk_mc, pk_mi, pk_rx, pk_cb;         // value offset in LDS | value length << 16
-};
+// (what the walk finds: AuxTags, record_core.h)
 // cls: aux value type -> 1 / 2 / 4 (fixed size), 8 (Z), 16 (H), 32 (B), 0 (unknown).  The table lies in device memory, built at compile time
 // (round 6): a wavefront copies it with one load and one LDS store.  Until round 5 every workgroup COMPUTED its 256 entries (a switch per
 // entry: ~190 vector instructions per wavefront — a quarter of k_split_parse's instructions per family, whose wavefronts live for one round
@@ -560,20 +562,8 @@ __global__ __launch_bounds__(NT) void k_family(FastParams P) {
           uint64_t clip = bam::mate_clip(v, ops, n_ops, mc_off >= 0 ? p + mc_off : nullptr, mc_len, mops, WG_MC_OPS, &overflow);
           if (overflow) bad = true;
           R.clip = (uint16_t)(clip > 65535 ? 65535 : clip);
-          // name hash for mate pairing (a filter: candidates are compared word by word below): whole 8-byte steps, then one step
-          // over the LAST 8 bytes (it may overlap)
-          {
-            const uint32_t nl = R.name_len;
-            uint32_t h = nl, i = 0;
-            for (; i + 8 <= nl; i += 8) { h = __builtin_rotateleft32(h, 5) ^ ld32u(dyn, lo_r + 32 + i); h = __builtin_rotateleft32(h, 11) + ld32u(dyn, lo_r + 36 + i); }
-            if (i < nl) {
-              uint32_t w0, w1;
-              if (nl >= 8) { w0 = ld32u(dyn, lo_r + 24 + nl); w1 = ld32u(dyn, lo_r + 28 + nl); }
-              else { const unsigned long long v = ld64u(dyn, lo_r + 32) & ((1ULL << (8 * nl)) - 1ULL); w0 = (uint32_t)v; w1 = (uint32_t)(v >> 32); }
-              h = __builtin_rotateleft32(h, 5) ^ w0; h = __builtin_rotateleft32(h, 11) + w1;
-            }
-            R.name_hash = h ^ (h >> 15) ^ (h << 7);
-          }
+          // name hash for mate pairing (a filter: candidates are compared word by word below)
+          R.name_hash = record::name_hash30(R.name_len, [&](uint32_t o) { return ld32u(dyn, lo_r + 32 + o); }, [&](uint32_t o) { return ld64u(dyn, lo_r + 32 + o); });
         }
       }
     }
@@ -1147,6 +1137,34 @@ inline void build_fw_image(FwLds& L, const ConsensusTables& t) {
 // CAP 1 (duplex, METH 0): the build of a caller with --max-reads-per-strand — a read set above the cap is scored over its `cap` lowest name ranks, walked in
 // (rank, file order), and the observations of ALL its reads are counted beside them for the duplex error recount (see 5D / 6D); CAP 0 is the kernel without any of it.
 // CAP 1 (CODEC): the build of a caller with --max-reads-per-strand — the R1 list and the R2 list are cut to their `cap` lowest name ranks ahead of the geometry (5C).
+// Wave-aggregated append of the columns (and UMI characters) whose call needs call_full to the global FullItem lists (k_call_full works through them
+// densely): one atomic with its return value per wavefront and list tried; a full list chains to the next one, only a globally full pool overflows.  Every
+// lane of the wavefront takes part; `obs_packed`: the four observation counts, a byte each.  Returns: this lane's item found no room (list overflow).
+__device__ __forceinline__ bool push_full_global(const FastParams& P, const uint32_t lane, const uint32_t my_list, const bool need, const uint64_t dest, const double* ll,
+                                                 const uint32_t obs_packed, const uint32_t chains) {
+  bool pending = need;
+  uint32_t l = my_list;
+  for (uint32_t tries = 0;; tries++) {
+    const unsigned long long m = __ballot(pending);
+    if (!m) return false;
+    if (tries >= N_LISTS) return pending;
+    const uint32_t cnt = (uint32_t)__popcll(m), leader = (uint32_t)__builtin_ctzll(m);
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(&P.full_count[l], cnt);
+    base = (uint32_t)__shfl((int)base, (int)leader);
+    if (pending) {
+      const uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+      if (idx < P.full_cap) {
+        FullItem* it = &P.full_items[(size_t)l * P.full_cap + idx];
+        it->dest = dest; it->ll[0] = ll[0]; it->ll[1] = ll[1]; it->ll[2] = ll[2]; it->ll[3] = ll[3];
+        it->obs = obs_packed; it->chains = chains;
+        pending = false;
+      }
+    }
+    l = (l + 1) & (N_LISTS - 1);
+  }
+}
+
 template <int MODE, int METH = 0, int CAP = 0>
 #ifndef FGX_WAVE_OCC_DUPLEX
 #define FGX_WAVE_OCC_DUPLEX 4   /* the duplex branch holds four column sets' worth of state beside the record lanes: at 5 waves per SIMD (96 VGPRs) its
@@ -1173,29 +1191,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   uint8_t* W = dyn + (size_t)wv * P.lds_wave_bytes;
   const uint32_t my_list = blockIdx.x & (N_LISTS - 1);
   bool list_overflow = false;
-  // wave-aggregated append of the columns whose call needs call_full (processed densely by k_call_full)
   auto push_full = [&](bool need, uint64_t dest, const double* ll, const uint32_t* obs) {
-    bool pending = need;
-    uint32_t l = my_list;
-    for (uint32_t tries = 0;; tries++) {           // a full list chains to the next one; only a globally full pool overflows
-      unsigned long long m = __ballot(pending);
-      if (!m) break;
-      if (tries >= N_LISTS) { list_overflow |= pending; break; }
-      uint32_t cnt = (uint32_t)__popcll(m), leader = (uint32_t)__builtin_ctzll(m);
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(&P.full_count[l], cnt);
-      base = __shfl(base, leader);
-      if (pending) {
-        uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (idx < P.full_cap) {
-          FullItem* it = &P.full_items[(size_t)l * P.full_cap + idx];
-          it->dest = dest; it->ll[0] = ll[0]; it->ll[1] = ll[1]; it->ll[2] = ll[2]; it->ll[3] = ll[3];
-          it->obs = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24); it->chains = 0;
-          pending = false;
-        }
-      }
-      l = (l + 1) & (N_LISTS - 1);
-    }
+    list_overflow |= push_full_global(P, lane, my_list, need, dest, ll, obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24), 0u);
   };
   unsigned long long* st = P.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * 32;
   const uint32_t r0 = P.grp_first[g], n = P.grp_first[g + 1] - r0;
@@ -1264,18 +1261,15 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   bool multi = false;               // (METH) the record has more than one CIGAR op
   uint32_t strand = 0;   // duplex: 1 = MI ends in /A, 2 = /B
   if (act) {
-    const uint32_t h2 = ld32u(W, lo + 8), h3 = ld32u(W, lo + 12);
-    const uint32_t l_name = h2 & 0xFF, n_cig = h3 & 0xFFFF;
-    l_seq = ld32u(W, lo + 16);
-    flags = h3 >> 16;
-    unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
-    unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
-    unsigned long long aux_off = qual_off + l_seq;
-    if (aux_off > len || l_seq > 65535 || l_name == 0) bad = true;
+    const record::FixedHeader H = record::decode_header(ld32u(W, lo), ld32u(W, lo + 4), ld32u(W, lo + 8), ld32u(W, lo + 12), ld32u(W, lo + 16));
+    const record::Layout lay = record::layout(H, len);
+    const uint32_t l_name = H.l_name, n_cig = H.n_cig;
+    l_seq = H.l_seq; flags = H.flags;
+    if (lay.odd) bad = true;
     else {
       name_len = l_name - 1;
-      ref_id = (int32_t)ld32u(W, lo); pos = (int32_t)ld32u(W, lo + 4);
-      seq_lo = lo + (uint32_t)seq_off; qual_lo = lo + (uint32_t)qual_off;
+      ref_id = H.ref_id; pos = H.pos;
+      seq_lo = lo + lay.seq_off; qual_lo = lo + lay.qual_off;
       excluded = (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) != 0;
       if (MODE == 1 && excluded) bad = true;   // the duplex caller has no secondary/supplementary filter: general path
       // (methylation-aware mode: column p of a read set lies at the anchor's pos + p, or at pos + T - 1 - p, only when the reference makes ONE M op of the
@@ -1298,42 +1292,38 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
           m_len = l_seq;
           if constexpr (METH != 0) tot_len = l_seq;
         } else if (MODE != 2 && n_cig <= MAX_CIG_OPS) {
-          uint32_t phase = 0, trail_s = 0;          // 0: leading clips, 1: aligned block, 2: trailing clips
-          bool okc = true;
+          record::CigarBlock cb = record::cigar_block_start();   // clips around one aligned block; I, D, N, P (cplx): the workgroup kernel
 #pragma unroll
           for (uint32_t i = 0; i < MAX_CIG_OPS; i++) {
             if (i >= n_cig) break;
-            const uint32_t o = ld32u(W, lo + 32 + l_name + 4 * i), t = o & 15, ln = o >> 4;
-            ops[i] = o;
-            if constexpr (METH != 0) { tot_len += ln; multi = true; }
-            if (t == 0 || t == 7 || t == 8) { if (phase == 2) okc = false; phase = 1; m_len += ln; }
-            else if (t == 4) { if (phase == 0) lead_s += ln; else { phase = 2; trail_s += ln; } }
-            else if (t == 5) { if (phase == 1) phase = 2; }
-            else { okc = false; if (t == 1 || t == 2 || t == 3 || t == 6) cplx = true; }   // I, D, N, P: the workgroup kernel
+            ops[i] = ld32u(W, lo + 32 + l_name + 4 * i);
+            record::cigar_block_op(cb, ops[i]);
           }
+          lead_s = cb.lead; m_len = cb.aln; cplx = cb.cplx;
+          if constexpr (METH != 0) { tot_len = cb.tot; multi = true; }
           if (cplx && MODE == 0) { /* decided below: the whole family moves to the workgroup-per-family kernel */ }
-          else if (!okc || m_len == 0 || m_len > 65535 || (unsigned long long)lead_s + m_len + trail_s != l_seq) bad = true;
+          else if (!record::cigar_block_fits(cb, l_seq) || m_len > 65535) bad = true;
           if (METH != 0 && tot_len > 65535u) bad = true;
         } else if (MODE == 0 && n_cig <= WG_CIG_OPS) { cplx = true; long_cigar = true; }   // (more ops than this kernel reads: the workgroup kernel's)
         else bad = true;
       }
       // aux walk in LDS (tags.rs:13-34): first occurrence of MC / <tag> / RX / <cell tag>
-      const uint32_t a0 = lo + (uint32_t)aux_off, an = len - (uint32_t)aux_off;
       AuxTags ax;
-      aux_walk(W, sTagCls, a0, an, P, ax);
+      aux_walk(W, sTagCls, lo + lay.aux_off, len - lay.aux_off, P, ax);
       if (ax.oddw) bad = true;
-      const bool has_mc = (ax.got & 1u) != 0;
-      const uint32_t mc_lo = ax.pk_mc & 0xFFFF, mc_len = ax.pk_mc >> 16;
-      has_mi = (ax.got & 2u) != 0; mi_lo = ax.pk_mi & 0xFFFF; mi_len = ax.pk_mi >> 16;
-      has_rx = (ax.got & 4u) != 0; rx_lo = ax.pk_rx & 0xFFFF; rx_len = ax.pk_rx >> 16;
-      has_cb = (ax.got & 8u) != 0; cb_lo = ax.pk_cb & 0xFFFF; cb_len = ax.pk_cb >> 16;
+      const record::TagFields tg = record::unpack_tags(ax);
+      const bool has_mc = tg.has_mc;
+      const uint32_t mc_lo = tg.mc_lo, mc_len = tg.mc_len;
+      has_mi = tg.has_mi; mi_lo = tg.mi_lo; mi_len = tg.mi_len;
+      has_rx = tg.has_rx; rx_lo = tg.rx_lo; rx_len = tg.rx_len;
+      has_cb = tg.has_cb; cb_lo = tg.cb_lo; cb_len = tg.cb_len;
       if (MODE == 1) {   // strand from the MI suffix; every paired read needs `<id>/A` or `<id>/B` (duplex_caller.rs:2557-2566: fatal otherwise)
         if (has_mi && mi_len >= 2 && W[mi_lo + mi_len - 2] == '/') { const uint8_t sc = W[mi_lo + mi_len - 1]; strand = sc == 'A' ? 1u : sc == 'B' ? 2u : 0u; }
         if ((flags & bam::F_PAIRED) && (strand == 0 || P.prefix_len + 1 + (mi_len - 2) >= 255)) bad = true;
       }
       if (MODE == 2 && !bad) {   // is_fr_pair_raw of THIS record (overlap.rs:21-69); only the reverse record's answer is used
         const int32_t mpos = (int32_t)ld32u(W, lo + 24), mref = (int32_t)ld32u(W, lo + 20);
-        if (pos >= (1 << 30) || mpos < -1 || mpos >= (1 << 30)) bad = true;
+        if (pos >= record::POS_LIMIT || mpos < -1 || mpos >= record::POS_LIMIT) bad = true;
         const bool rv = (flags & bam::F_REVERSE) != 0, mrv = (flags & bam::F_MATE_REVERSE) != 0;
         const bool okp = !(flags & bam::F_MATE_UNMAPPED) && ref_id == mref && rv != mrv;
         strand = (okp && ((long long)mpos + 1 < (long long)pos + 1 + ((long long)l_seq - 1))) ? 1u : 0u;   // `strand` doubles as frself here
@@ -1341,42 +1331,11 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       if (MODE != 2 && !bad && !excluded && !long_cigar && !unm) {
         // mate-overlap clip (raw-bam/overlap.rs:181-357).  Closed form when the MC tag is one M op and all
         // coordinates are in the ordinary range (no saturating arithmetic can trigger); general code otherwise.
-        bool fastclip = false;
-        uint32_t ML = 0;
-        if (n_cig == 1 && has_mc && mc_len >= 2 && mc_len <= 8) {
-          unsigned long long v = ld64u(W, mc_lo);
-          uint32_t k = 0, val = 0;
-          while (k < mc_len - 1) { uint32_t ch = (uint32_t)(v >> (8 * k)) & 0xFF; if (ch < '0' || ch > '9') break; val = val * 10 + (ch - '0'); k++; }
-          if (k == mc_len - 1 && ((v >> (8 * k)) & 0xFF) == 'M' && val > 0) { fastclip = true; ML = val; }
-        }
-        const int32_t mpos = (int32_t)ld32u(W, lo + 24);
-        if (fastclip && pos < (1 << 30) && mpos >= 0 && mpos < (1 << 30)) {
-          uint64_t cl = 0;
-          const int32_t mref = (int32_t)ld32u(W, lo + 20);
-          const bool rv = (flags & bam::F_REVERSE) != 0, mrv = (flags & bam::F_MATE_REVERSE) != 0;
-          const long long L = l_seq, tp = (long long)pos + 1, mp = (long long)mpos + 1;
-          bool fr = (flags & bam::F_PAIRED) && !(flags & bam::F_MATE_UNMAPPED) && ref_id == mref && rv != mrv;
-          if (fr) fr = rv ? (mp < tp + (L - 1)) : (tp < mp + ((long long)ML - 1));
-          if (fr) {
-            const long long read_end = tp - 1 + L, mate_end = mp - 1 + (long long)ML;
-            if (rv) {
-              if (!(tp > mate_end) && !(read_end < mp)) {
-                long long fs = tp > mp ? tp : mp;
-                long long rb = fs - tp; if (rb > L) rb = L;
-                long long mb = fs - mp; if (mb > (long long)ML) mb = ML;
-                cl = rb > mb ? (uint64_t)(rb - mb) : 0;
-              }
-            } else {
-              if (!(read_end < mp) && !(mate_end < tp)) {
-                long long ls = read_end < mate_end ? read_end : mate_end;
-                long long ra = ls - tp + 1; if (ra > L) ra = L;
-                long long ma = ls - mp + 1; if (ma > (long long)ML) ma = ML;
-                long long rp = L - ra, mq = (long long)ML - ma;
-                cl = rp > mq ? (uint64_t)(rp - mq) : 0;
-              }
-            }
-          }
-          clip = (uint32_t)(cl > 65535 ? 65535 : cl);
+        // (the guards of record::single_m_mate_clip: pos >= 0 and l_seq in 1 .. 65 535 hold for a record that is not bad, ML comes from at most seven digits)
+        const uint32_t ML = (n_cig == 1 && has_mc) ? record::mc_single_m(mc_len, [&]() { return ld64u(W, mc_lo); }) : 0u;
+        const record::MateFields M = record::decode_mate(ld32u(W, lo + 20), ld32u(W, lo + 24));
+        if (ML != 0 && pos < record::POS_LIMIT && record::mate_in_range(M)) {
+          clip = record::single_m_mate_clip(H, ref_id, M, (int32_t)ML);        // <= l_seq
         } else {
           uint32_t mops[MAX_MC_OPS];
           bool overflow = false;
@@ -2424,26 +2383,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   rj_notfr = n_notfr; s_filtered += n_notfr;
   // overlap clip against the mate in hand (overlap.rs:223-357 for two single-M alignments)
   if (fr) {
-    const long long L = l_seq, ML = m_lseq, tp = (long long)pos + 1, mp = (long long)m_pos + 1;
-    const long long read_end = tp - 1 + L, mate_end = mp - 1 + ML;
-    long long cl = 0;
-    if (rev) {
-      if (!(tp > mate_end) && !(read_end < mp)) {
-        const long long fs = tp > mp ? tp : mp;
-        long long rb = fs - tp; if (rb > L) rb = L;
-        long long mb = fs - mp; if (mb > ML) mb = ML;
-        cl = rb > mb ? rb - mb : 0;
-      }
-    } else {
-      if (!(read_end < mp) && !(mate_end < tp)) {
-        const long long ls = read_end < mate_end ? read_end : mate_end;
-        long long ra = ls - tp + 1; if (ra > L) ra = L;
-        long long ma = ls - mp + 1; if (ma > ML) ma = ML;
-        const long long rp = L - ra, mq = ML - ma;
-        cl = rp > mq ? rp - mq : 0;
-      }
-    }
-    clip = (uint32_t)cl;
+    // (the parse refused pos outside [0, 2^30) and l_seq outside 1 .. 65 535 for this record and for its mate: the closed form's ranges)
+    clip = record::single_m_overlap_clip(rev, pos, (int32_t)l_seq, m_pos, (int32_t)m_lseq);
   }
   // ClippedRecordInfo (:1006-1040): hard clip at the 3' end; a reverse read loses its start and moves right
   const uint32_t clen = fr ? (l_seq > clip ? l_seq - clip : 0) : 0;                 // clipped_seq_len = reference span of the clipped M

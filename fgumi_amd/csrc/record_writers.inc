@@ -33,6 +33,7 @@ struct EmitCtx {
 };
 
 // unaligned global dwords (gfx950 takes them in one instruction)
+// (the parsers' pair: gld32 / gld64, fastpath.hip — the same bodies; kept apart because sharing them moves k_emit's registers, profiles/record_core.md)
 __device__ __forceinline__ uint32_t gld32u(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ __forceinline__ uint2 gld64u(const uint8_t* p) { uint2 v; __builtin_memcpy(&v, p, 8); return v; }
 __device__ __forceinline__ void gst32u(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }

@@ -12,8 +12,8 @@
 // byte is loaded.  So the column kernel needs no LDS beside its tables, a CU holds as many wavefronts as registers allow, loads of
 // four rows are in flight together, and the family size is bounded by nothing but the counters' widths (255 reads per end).
 //
-//   k_deep_parse   thread = record, the family's per-record state in LDS arrays: k_simplex_wave2's record phases (shape checks, aux
-//                  walk, closed-form mate clip, name hash, mate pairing with names verified, shared span of each pair), the
+//   k_deep_parse   thread = record, the family's per-record state in LDS arrays: the record rules of record_core.h (shape checks, aux
+//                  walk, closed-form mate clip, name hash; deep_parse_records, shared with k_wide_parse), mate pairing with names verified, shared span of each pair, the
 //                  overlapping-bases COUNTERS (a wavefront per pair, lane = shared position), the final length of each read (its 3' end
 //                  walked back over what the pre-correction leaves there), the family gates, the member rows of each end in file
 //                  order (one 32-byte DeepRow per retained read) and everything of the EndDescs that does not depend on the columns.
@@ -121,6 +121,91 @@ struct DeepClipLds : DeepLds<MAXR> {
 template <uint32_t MAXR, int CLIPS> struct DeepLdsOf { typedef DeepLds<MAXR> type; };
 template <uint32_t MAXR> struct DeepLdsOf<MAXR, 1> { typedef DeepClipLds<MAXR> type; };
 
+// The parse of k_deep_parse and k_wide_parse (their phase 1): thread = record, the bytes straight from global memory, the rules of record_core.h.  S: the
+// per-record state (DeepLds, or WideRecs' arrays of the same names), C: the family's counters (`bad`: bit 0 some record is not this path's, bits 1 - 3 the
+// end holds an unmapped record; `multi` under CLIPS).  `take_unmapped`: an unmapped record without a CIGAR is in the shape (streaming_header_odd).
+template <int CLIPS, class Recs, class Cnt>
+__device__ __forceinline__ void deep_parse_records(const FastParams& P, Recs& S, Cnt& C, const uint32_t r0, const uint32_t n, const uint32_t tid, const uint32_t nt,
+                                                   const uint8_t* const sTagCls, const bool take_unmapped) {
+  for (uint32_t r = tid; r < n; r += nt) {
+    const unsigned long long off = P.rec_off[r0 + r];
+    const uint32_t len = P.rec_len[r0 + r];
+    bool odd = false;
+    uint32_t l_seq = 0, seq_rel = 0, name_len = 0, clip = 0, hash = 0, flags = 0, ty = 0;
+    int32_t pos = 0, ref_id = 0;
+    record::TagFields tg = {};
+    record::CigarBlock cb = record::cigar_block_start();   // (CLIPS) leading soft clip, aligned block, all ops
+    if (len < 36u || len > 0xFFFFu || off > P.blob_len || (unsigned long long)len > P.blob_len - off) odd = true;
+    else {
+      const uint8_t* const rec = P.blob + off;
+      const record::FixedHeader H = record::decode_header(gld32(rec), gld32(rec + 4), gld32(rec + 8), gld32(rec + 12), gld32(rec + 16));
+      const record::Layout lay = record::layout(H, len);
+      l_seq = H.l_seq; flags = H.flags;
+      const bool unm = (flags & bam::F_UNMAPPED) != 0;      // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused
+      if (lay.odd || record::streaming_header_odd(H, CLIPS != 0 ? WG_CIG_OPS : 1u, take_unmapped, 0u)) odd = true;
+      else {
+        name_len = H.l_name - 1;
+        ref_id = unm ? unmapped_ref_key(r) : H.ref_id; pos = H.pos;   // (no shared span with an unmapped member, phase 2)
+        seq_rel = lay.seq_off;
+        if (record::streaming_flags_odd(H, false)) odd = true;
+        if (!unm) {
+          const uint32_t op = gld32(rec + 32 + H.l_name);
+          if (CLIPS == 0 || H.n_cig == 1) {
+            if (!record::single_block_op(op, l_seq)) odd = true;
+            cb.aln = cb.tot = l_seq;
+          } else if constexpr (CLIPS != 0) {
+            // clips around one aligned block; I D N P are not this path's
+            for (uint32_t i = 0; i < H.n_cig; i++) record::cigar_block_op(cb, i == 0 ? op : gld32(rec + 32 + H.l_name + 4 * i));   // (at most 16 lengths below 2^28)
+            if (!record::cigar_block_fits(cb, l_seq) || cb.tot > 65535u) odd = true;
+            atomicOr(&C.multi, 1u);
+          }
+        }
+        AuxTags ax;
+        aux_walk(rec, sTagCls, lay.aux_off, len - lay.aux_off, P, ax);       // (offsets inside the record: below 2^16)
+        if (ax.oddw) odd = true;
+        tg = record::unpack_tags(ax);
+        if (r == 0 && record::first_record_odd(tg.has_mi, tg.mi_len, P.prefix_len)) odd = true;
+        if (!odd && tg.has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
+          const uint32_t ML = record::mc_single_m(tg.mc_len, [&]() { return gld64(rec + tg.mc_lo); });
+          const record::MateFields M = record::decode_mate(gld32(rec + 20), gld32(rec + 24));
+          const bool closed = ML != 0 && record::mate_in_range(M);   // this read's mate is one M op in the closed form's range
+          if (CLIPS != 0 && !(closed && H.n_cig == 1)) {
+            // the general rule on the ops.  Every function of it (bamrec.h: reference length, leading / trailing soft clip, query length, query bases
+            // up to a reference position, is_fr_pair) gives the same for H* S* (M|=|X)+ S* H* as for `lead S, block M, trail S`: hard clips count
+            // nowhere, soft clips are summed from either end, neighbouring aligned ops are walked as one — so three ops stand for the sixteen
+            uint32_t ops3[3] = {(cb.lead << 4) | 4u, cb.aln << 4, ((l_seq - cb.lead - cb.aln) << 4) | 4u};
+            uint32_t mops[MAX_MC_OPS];
+            bool overflow = false;
+            if (!odd) {
+              const bam::Rec v{rec, len};
+              const unsigned long long cl = bam::mate_clip(v, ops3, 3, rec + tg.mc_lo, tg.mc_len, mops, MAX_MC_OPS, &overflow);
+              if (overflow) odd = true;                        // (a mate of more ops than this kernel parses: the general path's)
+              clip = (uint32_t)(cl > 65535ull ? 65535ull : cl);
+            }
+          } else if (!closed) odd = true;
+          else clip = record::single_m_mate_clip(H, ref_id, M, (int32_t)ML);
+        }
+        if (!odd) {
+          hash = record::name_hash30(name_len, [&](uint32_t o) { return gld32(rec + 32 + o); }, [&](uint32_t o) { return gld64(rec + 32 + o); });
+          if (rec[lay.qual_off] == 0xFF) odd = true;                       // absent qualities (:1119-1124): the first one decides here
+          if (tg.has_rx && tg.rx_len > 255u) odd = true;
+        }
+        ty = !(flags & bam::F_PAIRED) ? 0u : (flags & bam::F_FIRST) ? 1u : 2u;
+      }
+    }
+    if (odd) C.bad = 1;
+    else if (flags & bam::F_UNMAPPED) atomicOr(&C.bad, 2u << ty);    // bits 1 - 3: the end holds an unmapped record
+    const uint32_t pt = odd ? 0u : (flags & bam::F_FIRST) ? 1u : (flags & bam::F_LAST) ? 2u : 0u;   // pair-map type (overlapping.rs:627-684)
+    S.off[r] = off; S.key[r] = (hash << 2) | pt; S.pos[r] = pos; S.ref_id[r] = ref_id;
+    S.l_seq[r] = (uint16_t)l_seq; S.seq_rel[r] = (uint16_t)seq_rel; S.name_len[r] = (uint16_t)name_len; S.clip[r] = (uint16_t)clip; S.final_len[r] = 0;
+    S.wo[r] = 0; S.mo[r] = 0; S.wc[r] = 0; S.partner[r] = -1;   // (no mate yet; WideRecs' unsigned array holds it as 0xFFFFFFFF)
+    if constexpr (CLIPS != 0) { S.lead[r] = (uint16_t)cb.lead; S.aln[r] = (uint16_t)cb.aln; S.tot[r] = (uint16_t)cb.tot; }
+    S.rx_rel[r] = (uint16_t)tg.rx_lo; S.cb_rel[r] = (uint16_t)tg.cb_lo; S.rx_len[r] = (uint8_t)tg.rx_len; S.cb_len[r] = (uint8_t)tg.cb_len;
+    S.bits[r] = (uint8_t)(ty | ((flags & bam::F_REVERSE) ? 4u : 0u) | (tg.has_rx ? 8u : 0u) | (tg.has_cb ? 16u : 0u) | ((flags & bam::F_LAST) ? 32u : 0u) |
+                         ((flags & bam::F_UNMAPPED) ? 64u : 0u));
+  }
+}
+
 // <NT, MAXR>: threads per workgroup and the records a family may have — <128, 128> and <256, 512> for the families above 64 records, <256, 1024>
 // for those of more than 512 under --max-reads (an end fits its 255 reads after the cut only), <64, 64> for everything else when the streaming
 // kernels are the whole pipeline (methylation-aware mode: a wavefront per family, 3 KB of LDS)
@@ -167,150 +252,9 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
   __syncthreads();
   const uint32_t min_bq = P.min_input_bq & 0xFFu;
 
-  // ---- 1. parse: thread = record (k_simplex_wave2's phase 2, the bytes straight from global memory) --------------------------------
-  for (uint32_t r = tid; r < n; r += DEEP_NT) {
-    const unsigned long long off = P.rec_off[r0 + r];
-    const uint32_t len = P.rec_len[r0 + r];
-    bool odd = false;
-    uint32_t l_seq = 0, seq_rel = 0, name_len = 0, clip = 0, hash = 0, flags = 0, ty = 0;
-    int32_t pos = 0, ref_id = 0;
-    uint32_t rx_rel = 0, rx_len = 0, cb_rel = 0, cb_len = 0;
-    bool has_mi = false, has_rx = false, has_cb = false;
-    uint32_t mi_len = 0;
-    uint32_t lead_s = 0, m_len = 0, tot_len = 0;   // (CLIPS) leading soft clip, aligned block, all ops
-    if (len < 36u || len > 0xFFFFu || off > P.blob_len || (unsigned long long)len > P.blob_len - off) odd = true;
-    else {
-      const uint8_t* const rec = P.blob + off;
-      const uint32_t h2 = gld32(rec + 8), h3 = gld32(rec + 12);
-      const uint32_t l_name = h2 & 0xFF, n_cig = h3 & 0xFFFF;
-      l_seq = gld32(rec + 16);
-      flags = h3 >> 16;
-      const unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
-      const unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
-      const unsigned long long aux_off = qual_off + l_seq;
-      // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>); the methylation-aware mode needs a position
-      const bool unm = (flags & bam::F_UNMAPPED) != 0;
-      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || (CLIPS != 0 ? (unm || n_cig == 0 || n_cig > WG_CIG_OPS) : n_cig != (unm ? 0u : 1u)) ||
-          (unm && P.meth_mode)) odd = true;
-      else {
-        name_len = l_name - 1;
-        ref_id = unm ? unmapped_ref_key(r) : (int32_t)gld32(rec); pos = (int32_t)gld32(rec + 4);   // (no shared span with an unmapped member, phase 2)
-        seq_rel = (uint32_t)seq_off;
-        if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
-        if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;   // counted, but in no end
-        if (!unm) {
-          if (pos < 0 || pos >= (1 << 30)) odd = true;
-          const uint32_t op = gld32(rec + 32 + l_name), t = op & 15;
-          if (CLIPS == 0 || n_cig == 1) {
-            if (!(t == 0 || t == 7 || t == 8) || (op >> 4) != l_seq) odd = true;
-            m_len = tot_len = l_seq;
-          } else if constexpr (CLIPS != 0) {
-            // clips around one aligned block (k_family_wave's walk): 0 leading clips, 1 the block, 2 trailing clips; I D N P are not this path's
-            uint32_t phase = 0, trail_s = 0;
-            bool okc = true;
-            for (uint32_t i = 0; i < n_cig; i++) {
-              const uint32_t o = i == 0 ? op : gld32(rec + 32 + l_name + 4 * i), ty = o & 15, ln = o >> 4;
-              tot_len += ln;                                   // (at most 16 lengths below 2^28)
-              if (ty == 0 || ty == 7 || ty == 8) { if (phase == 2) okc = false; phase = 1; m_len += ln; }
-              else if (ty == 4) { if (phase == 0) lead_s += ln; else { phase = 2; trail_s += ln; } }
-              else if (ty == 5) { if (phase == 1) phase = 2; }
-              else okc = false;
-            }
-            if (!okc || m_len == 0 || tot_len > 65535u || (unsigned long long)lead_s + m_len + trail_s != l_seq) odd = true;
-            atomicOr(&S.multi, 1u);
-          }
-        }
-        AuxTags ax;
-        aux_walk(rec, sTagCls, (uint32_t)aux_off, len - (uint32_t)aux_off, P, ax);       // (offsets inside the record: below 2^16)
-        if (ax.oddw) odd = true;
-        const bool has_mc = (ax.got & 1u) != 0;
-        const uint32_t mc_lo = ax.pk_mc & 0xFFFF, mc_len = ax.pk_mc >> 16;
-        has_mi = (ax.got & 2u) != 0; mi_len = ax.pk_mi >> 16;
-        has_rx = (ax.got & 4u) != 0; rx_rel = ax.pk_rx & 0xFFFF; rx_len = ax.pk_rx >> 16;
-        has_cb = (ax.got & 8u) != 0; cb_rel = ax.pk_cb & 0xFFFF; cb_len = ax.pk_cb >> 16;
-        if (r == 0 && (!has_mi || P.prefix_len + 1 + mi_len >= 255)) odd = true;   // fatal in the reference (vanilla_caller.rs:1897-1908, 1795-1797)
-        if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
-          // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are both one M op
-          bool simple = false;
-          int32_t ML = 0;
-          if (mc_len >= 2 && mc_len <= 8) {
-            const unsigned long long v = gld64(rec + mc_lo);
-            uint32_t k = 0, val = 0;
-            while (k < mc_len - 1) { const uint32_t ch = (uint32_t)(v >> (8 * k)) & 0xFF; if (ch < '0' || ch > '9') break; val = val * 10 + (ch - '0'); k++; }
-            if (k == mc_len - 1 && ((v >> (8 * k)) & 0xFF) == 'M' && val > 0) { simple = true; ML = (int32_t)val; }
-          }
-          const int32_t mpos = (int32_t)gld32(rec + 24);
-          if (CLIPS != 0 && !(simple && n_cig == 1 && mpos >= 0 && mpos < (1 << 30))) {
-            // the general rule on the ops.  Every function of it (bamrec.h: reference length, leading / trailing soft clip, query length, query bases
-            // up to a reference position, is_fr_pair) gives the same for H* S* (M|=|X)+ S* H* as for `lead S, block M, trail S`: hard clips count
-            // nowhere, soft clips are summed from either end, neighbouring aligned ops are walked as one — so three ops stand for the sixteen
-            uint32_t ops3[3] = {(lead_s << 4) | 4u, m_len << 4, ((l_seq - lead_s - m_len) << 4) | 4u};
-            uint32_t mops[MAX_MC_OPS];
-            bool overflow = false;
-            if (!odd) {
-              const bam::Rec v{rec, len};
-              const unsigned long long cl = bam::mate_clip(v, ops3, 3, rec + mc_lo, mc_len, mops, MAX_MC_OPS, &overflow);
-              if (overflow) odd = true;                        // (a mate of more ops than this kernel parses: the general path's)
-              clip = (uint32_t)(cl > 65535ull ? 65535ull : cl);
-            }
-          } else if (!simple || mpos < 0 || mpos >= (1 << 30)) odd = true;
-          else {
-            int32_t cl = 0;
-            const int32_t mref = (int32_t)gld32(rec + 20);
-            const bool rv = (flags & bam::F_REVERSE) != 0, mrv = (flags & bam::F_MATE_REVERSE) != 0;
-            const int32_t L = (int32_t)l_seq, tp = pos + 1, mp = mpos + 1;
-            bool fr = (flags & bam::F_PAIRED) && !(flags & bam::F_MATE_UNMAPPED) && ref_id == mref && rv != mrv;
-            if (fr) fr = rv ? (mp < tp + (L - 1)) : (tp < mp + (ML - 1));
-            if (fr) {
-              const int32_t read_end = tp - 1 + L, mate_end = mp - 1 + ML;
-              if (rv) {
-                if (!(tp > mate_end) && !(read_end < mp)) {
-                  const int32_t fs = tp > mp ? tp : mp;
-                  int32_t rb = fs - tp; if (rb > L) rb = L;
-                  int32_t mb = fs - mp; if (mb > ML) mb = ML;
-                  cl = rb > mb ? rb - mb : 0;
-                }
-              } else {
-                if (!(read_end < mp) && !(mate_end < tp)) {
-                  const int32_t ls = read_end < mate_end ? read_end : mate_end;
-                  int32_t ra = ls - tp + 1; if (ra > L) ra = L;
-                  int32_t ma = ls - mp + 1; if (ma > ML) ma = ML;
-                  const int32_t rp = L - ra, mq = ML - ma;
-                  cl = rp > mq ? rp - mq : 0;
-                }
-              }
-            }
-            clip = (uint32_t)cl;
-          }
-        }
-        if (!odd) {
-          // 30-bit name hash for mate pairing: a filter only, candidates are compared byte by byte below (k_simplex_wave2's)
-          uint32_t h = name_len, i = 0;
-          for (; i + 8 <= name_len; i += 8) { h = __builtin_rotateleft32(h, 5) ^ gld32(rec + 32 + i); h = __builtin_rotateleft32(h, 11) + gld32(rec + 36 + i); }
-          if (i < name_len) {
-            uint32_t w0, w1;
-            if (name_len >= 8) { w0 = gld32(rec + 24 + name_len); w1 = gld32(rec + 28 + name_len); }
-            else { const unsigned long long v = gld64(rec + 32) & ((1ULL << (8 * name_len)) - 1ULL); w0 = (uint32_t)v; w1 = (uint32_t)(v >> 32); }
-            h = __builtin_rotateleft32(h, 5) ^ w0; h = __builtin_rotateleft32(h, 11) + w1;
-          }
-          hash = h ^ (h >> 15) ^ (h << 7);
-          if (rec[(uint32_t)qual_off] == 0xFF) odd = true;                 // absent qualities (:1119-1124): the first one decides here
-          if (has_rx && rx_len > 255u) odd = true;
-        }
-        ty = !(flags & bam::F_PAIRED) ? 0u : (flags & bam::F_FIRST) ? 1u : 2u;
-      }
-    }
-    if (odd) S.bad = 1;
-    else if (flags & bam::F_UNMAPPED) atomicOr(&S.bad, 2u << ty);    // bits 1 - 3: the end holds an unmapped record
-    const uint32_t pt = odd ? 0u : (flags & bam::F_FIRST) ? 1u : (flags & bam::F_LAST) ? 2u : 0u;   // pair-map type (overlapping.rs:627-684)
-    S.off[r] = off; S.key[r] = (hash << 2) | pt; S.pos[r] = pos; S.ref_id[r] = ref_id;
-    S.l_seq[r] = (uint16_t)l_seq; S.seq_rel[r] = (uint16_t)seq_rel; S.name_len[r] = (uint16_t)name_len; S.clip[r] = (uint16_t)clip; S.final_len[r] = 0;
-    S.wo[r] = 0; S.mo[r] = 0; S.wc[r] = 0; S.partner[r] = -1;
-    if constexpr (CLIPS != 0) { S.lead[r] = (uint16_t)lead_s; S.aln[r] = (uint16_t)m_len; S.tot[r] = (uint16_t)tot_len; }
-    S.rx_rel[r] = (uint16_t)rx_rel; S.cb_rel[r] = (uint16_t)cb_rel; S.rx_len[r] = (uint8_t)rx_len; S.cb_len[r] = (uint8_t)cb_len;
-    S.bits[r] = (uint8_t)(ty | ((flags & bam::F_REVERSE) ? 4u : 0u) | (has_rx ? 8u : 0u) | (has_cb ? 16u : 0u) | ((flags & bam::F_LAST) ? 32u : 0u) |
-                         ((flags & bam::F_UNMAPPED) ? 64u : 0u));
-  }
+  // ---- 1. parse: thread = record --------------------------------------------------------------------------------------------------------
+  // (DeepLds holds the per-record arrays AND the family's counters: S is both arguments; k_wide_parse passes its global arrays and its LDS counters)
+  deep_parse_records<CLIPS>(P, S, S, r0, n, tid, DEEP_NT, sTagCls, CLIPS == 0 && !P.meth_mode);
   __syncthreads();
   if (S.bad & 1u) { leave(); return; }
   if (S.bad >> 1) {
@@ -653,29 +597,8 @@ __global__ __launch_bounds__(256, FGX_DEEP_OCC) void k_deep_cols(FastParams P, D
   const DeviceTables* T = P.T;
   const uint32_t my_list = blockIdx.x & (N_LISTS - 1);
   bool list_overflow = false;
-  // an item straight into one of the global lists (k_simplex_wave2's push_direct)
-  auto push_item = [&](bool need, uint64_t dest, const double* ll, uint32_t obs_packed, uint32_t chains) {
-    bool pending = need;
-    uint32_t l = my_list;
-    for (uint32_t tries = 0;; tries++) {
-      const unsigned long long m = __ballot(pending);
-      if (!m) break;
-      if (tries >= N_LISTS) { list_overflow |= pending; break; }
-      const uint32_t cnt = (uint32_t)__popcll(m), leader = (uint32_t)__builtin_ctzll(m);
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(&P.full_count[l], cnt);
-      base = (uint32_t)__shfl((int)base, (int)leader);
-      if (pending) {
-        const uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (idx < P.full_cap) {
-          FullItem* it = &P.full_items[(size_t)l * P.full_cap + idx];
-          it->dest = dest; it->ll[0] = ll[0]; it->ll[1] = ll[1]; it->ll[2] = ll[2]; it->ll[3] = ll[3];
-          it->obs = obs_packed; it->chains = chains;
-          pending = false;
-        }
-      }
-      l = (l + 1) & (N_LISTS - 1);
-    }
+  auto push_item = [&](bool need, uint64_t dest, const double* ll, uint32_t obs_packed, uint32_t chains) {   // an item straight into one of the global lists
+    list_overflow |= push_full_global(P, lane, my_list, need, dest, ll, obs_packed, chains);
   };
   // The rows of an end are read through the scalar unit (constant address space: one s_load_dwordx8 per row, its fields in scalar registers —
   // every address below is `scalar base + this lane's index`); k_deep_parse wrote them, a kernel boundary ago.

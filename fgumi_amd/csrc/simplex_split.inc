@@ -102,8 +102,6 @@ __device__ __forceinline__ uint32_t s2_mul24(uint32_t a, uint32_t b) { return (a
 __device__ __forceinline__ uint32_t s2_mul24(uint32_t a, uint32_t b) { uint32_t r; asm("v_mul_u32_u24_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 #endif
 __device__ __forceinline__ uint32_t mbcnt64(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }   // bits of m below this lane
-__device__ __forceinline__ uint32_t gld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ unsigned long long gld64(const uint8_t* p) { unsigned long long v; __builtin_memcpy(&v, p, 8); return v; }
 
 // -----------------------------------------------------------------------------------------------------------------------------
 // k_split_parse — lane = record, 64 records (a run of whole families) per round
@@ -178,7 +176,7 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
     auto fbal = [&](bool p) -> unsigned long long { return (__ballot(p) >> seg_lo) & nmask; };   // the family's part of a ballot, bit i = its record i
     auto fbc = [&](uint32_t v, uint32_t s) -> uint32_t { return (uint32_t)__shfl((int)v, (int)(seg_lo + s)); };   // value of the family's record s
 
-    // ---- parse (k_simplex_wave2's phase 2; the bytes come through the two LDS windows) ------------------------------------------
+    // ---- parse (the record rules: record_core.h; the bytes come through the two LDS windows) -------------------------------------
     const unsigned long long off = act ? P.rec_off[r] : 0ull;
     const uint32_t len = act ? P.rec_len[r] : 0u;
     bool odd = false;
@@ -194,18 +192,17 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
     int32_t pos = 0, ref_id = 0;
     uint32_t mi_rel = 0, mi_len = 0, rx_rel = 0, rx_len = 0, cb_rel = 0, cb_len = 0;
     bool has_mi = false, has_rx = false, has_cb = false;
-    // fixed header: ref_id, pos, l_read_name | mapq | bin, n_cigar | flag ; l_seq, next ref, next pos, tlen
-    const uint32_t l_name = hp[0].z & 0xFF, n_cig = hp[0].w & 0xFFFF;
-    const bool unm = live && ((hp[0].w >> 16) & bam::F_UNMAPPED);   // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>)
+    // the fixed header, from the registers (a record that is not live: zeros)
+    const record::FixedHeader H = record::decode_header(hp[0].x, hp[0].y, hp[0].z, hp[0].w, hp[1].x);
+    const record::MateFields M = record::decode_mate(hp[1].y, hp[1].z);
+    const uint32_t l_name = H.l_name;
+    const bool unm = live && (H.flags & bam::F_UNMAPPED);   // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused
     uint32_t aux_rel = 0, aux_len = 0;
     if (live) {
-      l_seq = hp[1].x;
-      flags = hp[0].w >> 16;
-      const unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
-      const unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
-      const unsigned long long aux_off = qual_off + l_seq;
-      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u) || l_name + 4u > SP_HEAD) odd = true;   // (a name beyond the head window: rare, k_simplex_wave2's)
-      else { aux_rel = (uint32_t)aux_off; aux_len = len - aux_rel; seq_rel = (uint32_t)seq_off; name_len = l_name - 1; }
+      l_seq = H.l_seq; flags = H.flags;
+      const record::Layout lay = record::layout(H, len);
+      if (lay.odd || record::streaming_header_odd(H, 1u, true, SP_HEAD)) odd = true;   // (a name beyond the head window: rare, k_simplex_wave2's)
+      else { aux_rel = lay.aux_off; aux_len = len - aux_rel; seq_rel = lay.seq_off; name_len = l_name - 1; }
     }
     const bool parse = live && !odd;
     const bool aux_in_lds = aux_len <= SP_AUX;
@@ -218,88 +215,27 @@ __device__ __forceinline__ void s2_parse_wave(const FastParams& P, const uint32_
     }
     wave_sync();
     if (parse) {
-      ref_id = unm ? unmapped_ref_key(lane) : (int32_t)hp[0].x; pos = (int32_t)hp[0].y;   // (no shared span with an unmapped member: `ov_cnt` stays 0 below)
-      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
-      if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;   // counted, but in no end
-      if (!(flags & bam::F_PAIRED) && (flags & (bam::F_FIRST | bam::F_LAST))) odd = true;  // a fragment for the caller, a mate for the overlap step
-      if (!unm) {
-        if (pos < 0 || pos >= (1 << 30)) odd = true;
-        const uint32_t op = ld32u(Wh, l_name), ty = op & 15;
-        if (!(ty == 0 || ty == 7 || ty == 8) || (op >> 4) != l_seq) odd = true;
-      }
+      ref_id = unm ? unmapped_ref_key(lane) : H.ref_id; pos = H.pos;   // (no shared span with an unmapped member: `ov_cnt` stays 0 below)
+      if (record::streaming_flags_odd(H, true)) odd = true;
+      if (!unm && !record::single_block_op(ld32u(Wh, l_name), l_seq)) odd = true;
       // aux walk (tags.rs:13-34): first occurrence of MC / <tag> / RX / <cell tag>; value offsets relative to the tag block
       AuxTags ax;
       if (aux_in_lds) aux_walk(Wa, sTagCls, 0u, aux_len, P, ax);
       else aux_walk(rec + aux_rel, sTagCls, 0u, aux_len, P, ax);
       if (ax.oddw) odd = true;
-      const bool has_mc = (ax.got & 1u) != 0;
-      const uint32_t mc_o = ax.pk_mc & 0xFFFF, mc_len = ax.pk_mc >> 16;
-      has_mi = (ax.got & 2u) != 0; mi_rel = aux_rel + (ax.pk_mi & 0xFFFF); mi_len = ax.pk_mi >> 16;
-      has_rx = (ax.got & 4u) != 0; rx_rel = aux_rel + (ax.pk_rx & 0xFFFF); rx_len = ax.pk_rx >> 16;
-      has_cb = (ax.got & 8u) != 0; cb_rel = aux_rel + (ax.pk_cb & 0xFFFF); cb_len = ax.pk_cb >> 16;
-      if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
-        // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are one M op each
-        bool simple = false;
-        int32_t ML = 0;                                       // all terms below 2^30 + 10^7 + 2^16: 32-bit signed arithmetic is exact
-        if (mc_len >= 2 && mc_len <= 8) {
-          const unsigned long long v = aux_in_lds ? ld64u(Wa, mc_o) : gld64(rec + aux_rel + mc_o);
-          uint32_t k = 0, val = 0;
-          while (k < mc_len - 1) { const uint32_t ch = (uint32_t)(v >> (8 * k)) & 0xFF; if (ch < '0' || ch > '9') break; val = val * 10 + (ch - '0'); k++; }
-          if (k == mc_len - 1 && ((v >> (8 * k)) & 0xFF) == 'M' && val > 0) { simple = true; ML = (int32_t)val; }
-        }
-        const int32_t mpos = (int32_t)hp[1].z;
-        if (!simple || mpos < 0 || mpos >= (1 << 30)) odd = true;
-        else {
-          int32_t cl = 0;
-          const int32_t mref = (int32_t)hp[1].y;
-          const bool rv = (flags & bam::F_REVERSE) != 0, mrv = (flags & bam::F_MATE_REVERSE) != 0;
-          const int32_t L = (int32_t)l_seq, tp = pos + 1, mp = mpos + 1;
-          bool fr = (flags & bam::F_PAIRED) && !(flags & bam::F_MATE_UNMAPPED) && ref_id == mref && rv != mrv;
-          if (fr) fr = rv ? (mp < tp + (L - 1)) : (tp < mp + (ML - 1));
-          if (fr) {
-            const int32_t read_end = tp - 1 + L, mate_end = mp - 1 + ML;
-            if (rv) {
-              if (!(tp > mate_end) && !(read_end < mp)) {
-                const int32_t fs = tp > mp ? tp : mp;
-                int32_t rbb = fs - tp; if (rbb > L) rbb = L;
-                int32_t mb = fs - mp; if (mb > ML) mb = ML;
-                cl = rbb > mb ? rbb - mb : 0;
-              }
-            } else {
-              if (!(read_end < mp) && !(mate_end < tp)) {
-                const int32_t ls = read_end < mate_end ? read_end : mate_end;
-                int32_t raa = ls - tp + 1; if (raa > L) raa = L;
-                int32_t ma = ls - mp + 1; if (ma > ML) ma = ML;
-                const int32_t rp = L - raa, mq = ML - ma;
-                cl = rp > mq ? rp - mq : 0;
-              }
-            }
-          }
-          clip = (uint32_t)cl;                              // <= l_seq <= 65535
-        }
+      const record::TagFields tg = record::unpack_tags(ax);
+      has_mi = tg.has_mi; mi_rel = aux_rel + tg.mi_lo; mi_len = tg.mi_len;
+      has_rx = tg.has_rx; rx_rel = aux_rel + tg.rx_lo; rx_len = tg.rx_len;
+      has_cb = tg.has_cb; cb_rel = aux_rel + tg.cb_lo; cb_len = tg.cb_len;
+      if (!odd && tg.has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
+        // this read and its mate are both one M op, the mate in [0, 2^30): the closed form; anything else is not this kernel's
+        const uint32_t ML = record::mc_single_m(tg.mc_len, [&]() { return aux_in_lds ? ld64u(Wa, tg.mc_lo) : gld64(rec + aux_rel + tg.mc_lo); });
+        if (ML == 0 || !record::mate_in_range(M)) odd = true;
+        else clip = record::single_m_mate_clip(H, ref_id, M, (int32_t)ML);        // <= l_seq <= 65535
       }
-      if (!odd) {
-        // 30-bit name hash for mate pairing: a filter only, candidates are compared byte by byte below
-        uint32_t h = name_len;
-        uint32_t i = 0;
-        for (; i + 8 <= name_len; i += 8) {                 // whole 8-byte steps, then one step over the LAST 8 bytes (it may overlap)
-          h = __builtin_rotateleft32(h, 5) ^ ld32u(Wh, i);
-          h = __builtin_rotateleft32(h, 11) + ld32u(Wh, 4 + i);
-        }
-        if (i < name_len) {
-          uint32_t w0, w1;
-          if (name_len >= 8) { w0 = ld32u(Wh, name_len - 8); w1 = ld32u(Wh, name_len - 4); }
-          else {
-            const unsigned long long v = ld64u(Wh, 0) & ((1ULL << (8 * name_len)) - 1ULL);
-            w0 = (uint32_t)v; w1 = (uint32_t)(v >> 32);
-          }
-          h = __builtin_rotateleft32(h, 5) ^ w0;
-          h = __builtin_rotateleft32(h, 11) + w1;
-        }
-        hash = h ^ (h >> 15) ^ (h << 7);
-      }
+      if (!odd) hash = record::name_hash30(name_len, [&](uint32_t o) { return ld32u(Wh, o); }, [&](uint32_t o) { return ld64u(Wh, o); });
     }
-    if (act && sl == 0 && !odd && (!has_mi || P.prefix_len + 1 + mi_len >= 255)) odd = true;   // fatal in the reference (vanilla_caller.rs:1897-1908, 1795-1797)
+    if (act && sl == 0 && !odd && record::first_record_odd(has_mi, mi_len, P.prefix_len)) odd = true;
     if (act && !odd && (mi_len > 255 || rx_len > 255 || cb_len > 255)) odd = true;
     const bool rev = (flags & bam::F_REVERSE) != 0;
     const uint32_t ty = (!act || odd) ? 0u : (flags & bam::F_FIRST) ? 1u : (flags & bam::F_LAST) ? 2u : 0u;

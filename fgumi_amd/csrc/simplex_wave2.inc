@@ -137,27 +137,7 @@ __global__ __launch_bounds__(256, FGX_V2_OCC) void k_simplex_wave2(FastParams P,
   // an item straight into one of the global lists: one atomic WITH its return value per call (a memory round trip the wavefront
   // sits out) — the fallback of the wave-local list below
   auto push_direct = [&](bool need, uint64_t dest, const double* ll, uint32_t obs_packed, uint32_t chains) {
-    bool pending = need;
-    uint32_t l = my_list;
-    for (uint32_t tries = 0;; tries++) {
-      unsigned long long m = __ballot(pending);
-      if (!m) break;
-      if (tries >= N_LISTS) { list_overflow |= pending; break; }
-      uint32_t cnt = (uint32_t)__popcll(m), leader = (uint32_t)__builtin_ctzll(m);
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(&P.full_count[l], cnt);
-      base = __shfl(base, leader);
-      if (pending) {
-        uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (idx < P.full_cap) {
-          FullItem* it = &P.full_items[(size_t)l * P.full_cap + idx];
-          it->dest = dest; it->ll[0] = ll[0]; it->ll[1] = ll[1]; it->ll[2] = ll[2]; it->ll[3] = ll[3];
-          it->obs = obs_packed; it->chains = chains;
-          pending = false;
-        }
-      }
-      l = (l + 1) & (N_LISTS - 1);
-    }
+    list_overflow |= push_full_global(P, lane, my_list, need, dest, ll, obs_packed, chains);
   };
   unsigned long long* st = P.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * 32;
   // the family's descriptor (k_col_bound) and its first record index: one memory round trip; the record table and the records
@@ -240,102 +220,37 @@ __global__ __launch_bounds__(256, FGX_V2_OCC) void k_simplex_wave2(FastParams P,
   uint32_t mi_lo = 0, mi_len = 0, rx_lo = 0, rx_len = 0, cb_lo = 0, cb_len = 0;   // LDS offsets of tag values
   bool has_mi = false, has_rx = false, has_cb = false, odd = false;
   if (act) {
-    const uint32_t h2 = ld32u(W, lo + 8), h3 = ld32u(W, lo + 12);
-    const uint32_t l_name = h2 & 0xFF, n_cig = h3 & 0xFFFF;
-    l_seq = ld32u(W, lo + 16);
-    flags = h3 >> 16;
-    const unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
-    const unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
-    const unsigned long long aux_off = qual_off + l_seq;
-    const bool unm = (flags & bam::F_UNMAPPED) != 0;          // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused (k_family_wave<0>)
-    if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u)) odd = true;
+    const record::FixedHeader H = record::decode_header(ld32u(W, lo), ld32u(W, lo + 4), ld32u(W, lo + 8), ld32u(W, lo + 12), ld32u(W, lo + 16));
+    const record::Layout lay = record::layout(H, len);
+    l_seq = H.l_seq; flags = H.flags;
+    const bool unm = (flags & bam::F_UNMAPPED) != 0;          // an unmapped record: a read without a CIGAR — l_seq query bases, ref_id / pos unused
+    if (lay.odd || record::streaming_header_odd(H, 1u, true, 0u)) odd = true;
     else {
-      name_len = l_name - 1;
-      ref_id = unm ? unmapped_ref_key(lane) : (int32_t)ld32u(W, lo); pos = (int32_t)ld32u(W, lo + 4);
-      seq_lo = lo + (uint32_t)seq_off; qual_lo = lo + (uint32_t)qual_off;
-      if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
-      if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;   // counted, but in no end
-      if (!unm) {
-        if (pos < 0 || pos >= (1 << 30)) odd = true;
-        const uint32_t op = ld32u(W, lo + 32 + l_name), ty = op & 15;
-        if (!(ty == 0 || ty == 7 || ty == 8) || (op >> 4) != l_seq) odd = true;
-      }
+      name_len = H.l_name - 1;
+      ref_id = unm ? unmapped_ref_key(lane) : H.ref_id; pos = H.pos;
+      seq_lo = lo + lay.seq_off; qual_lo = lo + lay.qual_off;
+      if (record::streaming_flags_odd(H, false)) odd = true;
+      if (!unm && !record::single_block_op(ld32u(W, lo + 32 + H.l_name), l_seq)) odd = true;
       // aux walk in LDS (tags.rs:13-34): first occurrence of MC / <tag> / RX / <cell tag>
-      const uint32_t a0 = lo + (uint32_t)aux_off, an = len - (uint32_t)aux_off;
       AuxTags ax;
-      aux_walk(W, sTagCls, a0, an, P, ax);
+      aux_walk(W, sTagCls, lo + lay.aux_off, len - lay.aux_off, P, ax);
       if (ax.oddw) odd = true;
-      const bool has_mc = (ax.got & 1u) != 0;
-      const uint32_t mc_lo = ax.pk_mc & 0xFFFF, mc_len = ax.pk_mc >> 16;
-      has_mi = (ax.got & 2u) != 0; mi_lo = ax.pk_mi & 0xFFFF; mi_len = ax.pk_mi >> 16;
-      has_rx = (ax.got & 4u) != 0; rx_lo = ax.pk_rx & 0xFFFF; rx_len = ax.pk_rx >> 16;
-      has_cb = (ax.got & 8u) != 0; cb_lo = ax.pk_cb & 0xFFFF; cb_len = ax.pk_cb >> 16;
-      if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
-        // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are both one M op
-        // (k_family_wave<0> derives it; the general rules live there)
-        bool simple = false;
-        int32_t ML = 0;                                       // all terms below 2^30 + 10^7 + 2^16: 32-bit signed arithmetic is exact
-        if (mc_len >= 2 && mc_len <= 8) {
-          unsigned long long v = ld64u(W, mc_lo);
-          uint32_t k = 0, val = 0;
-          while (k < mc_len - 1) { uint32_t ch = (uint32_t)(v >> (8 * k)) & 0xFF; if (ch < '0' || ch > '9') break; val = val * 10 + (ch - '0'); k++; }
-          if (k == mc_len - 1 && ((v >> (8 * k)) & 0xFF) == 'M' && val > 0) { simple = true; ML = (int32_t)val; }
-        }
-        const int32_t mpos = (int32_t)ld32u(W, lo + 24);
-        if (!simple || mpos < 0 || mpos >= (1 << 30)) odd = true;
-        else {
-          int32_t cl = 0;
-          const int32_t mref = (int32_t)ld32u(W, lo + 20);
-          const bool rv = (flags & bam::F_REVERSE) != 0, mrv = (flags & bam::F_MATE_REVERSE) != 0;
-          const int32_t L = (int32_t)l_seq, tp = pos + 1, mp = mpos + 1;
-          bool fr = (flags & bam::F_PAIRED) && !(flags & bam::F_MATE_UNMAPPED) && ref_id == mref && rv != mrv;
-          if (fr) fr = rv ? (mp < tp + (L - 1)) : (tp < mp + (ML - 1));
-          if (fr) {
-            const int32_t read_end = tp - 1 + L, mate_end = mp - 1 + ML;
-            if (rv) {
-              if (!(tp > mate_end) && !(read_end < mp)) {
-                int32_t fs = tp > mp ? tp : mp;
-                int32_t rb = fs - tp; if (rb > L) rb = L;
-                int32_t mb = fs - mp; if (mb > ML) mb = ML;
-                cl = rb > mb ? rb - mb : 0;
-              }
-            } else {
-              if (!(read_end < mp) && !(mate_end < tp)) {
-                int32_t ls = read_end < mate_end ? read_end : mate_end;
-                int32_t ra = ls - tp + 1; if (ra > L) ra = L;
-                int32_t ma = ls - mp + 1; if (ma > ML) ma = ML;
-                int32_t rp = L - ra, mq = ML - ma;
-                cl = rp > mq ? rp - mq : 0;
-              }
-            }
-          }
-          clip = (uint32_t)cl;                              // <= l_seq <= 65535
-        }
+      const record::TagFields tg = record::unpack_tags(ax);
+      has_mi = tg.has_mi; mi_lo = tg.mi_lo; mi_len = tg.mi_len;
+      has_rx = tg.has_rx; rx_lo = tg.rx_lo; rx_len = tg.rx_len;
+      has_cb = tg.has_cb; cb_lo = tg.cb_lo; cb_len = tg.cb_len;
+      if (!odd && tg.has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {   // (either of them: no clip, whatever MC says)
+        // this read and its mate are both one M op, the mate in [0, 2^30): the closed form; anything else is not this kernel's
+        const uint32_t ML = record::mc_single_m(tg.mc_len, [&]() { return ld64u(W, tg.mc_lo); });
+        const record::MateFields M = record::decode_mate(ld32u(W, lo + 20), ld32u(W, lo + 24));
+        if (ML == 0 || !record::mate_in_range(M)) odd = true;
+        else clip = record::single_m_mate_clip(H, ref_id, M, (int32_t)ML);        // <= l_seq <= 65535
       }
-      if (!odd) {
-        // 30-bit name hash for mate pairing: a filter only, candidates are compared byte by byte below
-        uint32_t h = name_len;                                // (rotate / xor / add only: 32-bit multiplies are quarter rate)
-        uint32_t i = 0;
-        for (; i + 8 <= name_len; i += 8) {                   // whole 8-byte steps, then one step over the LAST 8 bytes (it may overlap)
-          h = __builtin_rotateleft32(h, 5) ^ ld32u(W, lo + 32 + i);
-          h = __builtin_rotateleft32(h, 11) + ld32u(W, lo + 36 + i);
-        }
-        if (i < name_len) {
-          uint32_t w0, w1;
-          if (name_len >= 8) { w0 = ld32u(W, lo + 24 + name_len); w1 = ld32u(W, lo + 28 + name_len); }
-          else {
-            const unsigned long long v = ld64u(W, lo + 32) & ((1ULL << (8 * name_len)) - 1ULL);
-            w0 = (uint32_t)v; w1 = (uint32_t)(v >> 32);
-          }
-          h = __builtin_rotateleft32(h, 5) ^ w0;
-          h = __builtin_rotateleft32(h, 11) + w1;
-        }
-        hash = h ^ (h >> 15) ^ (h << 7);
-      }
+      if (!odd) hash = record::name_hash30(name_len, [&](uint32_t o) { return ld32u(W, lo + 32 + o); }, [&](uint32_t o) { return ld64u(W, lo + 32 + o); });
     }
   }
   const uint32_t mi0_lo = rlane(mi_lo, 0), mi0_len = rlane(mi_len, 0);
-  if (lane == 0 && (!has_mi || P.prefix_len + 1 + mi_len >= 255)) odd = true;   // fatal in the reference (vanilla_caller.rs:1897-1908, 1795-1797)
+  if (lane == 0 && record::first_record_odd(has_mi, mi_len, P.prefix_len)) odd = true;
   if (act && !odd && W[qual_lo] == 0xFF) odd = true;                              // absent qualities (:1119-1124): the first one decides here
   if (__any(odd)) { to_old(); return; }
   if (__any(act && (flags & bam::F_UNMAPPED)) && mixed_unmapped_end(act, flags, [](bool p) { return __ballot(p); })) { to_old(); return; }

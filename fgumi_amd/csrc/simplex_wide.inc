@@ -7,7 +7,7 @@
 // kernel itself (call_full, consensus_math.h): in a family this deep nearly every column shows a second base, so every lane needs the chain anyway, and
 // FullItem and k_call_full stay as they are.
 //
-//   k_wide_parse   a workgroup per family: k_deep_parse<.., .., 0>'s phases in its order, with its counters and refusals.  The per-record state lies
+//   k_wide_parse   a workgroup per family: k_deep_parse<.., .., 0>'s phases in its order (the parse is the same function, deep_parse_records), with its counters and refusals.  The per-record state lies
 //                  in a global scratch (struct of arrays; a family's slice starts at the scan of the listed families' record counts, where its rows
 //                  start too); LDS holds only what the inner loops read again for every record: the pairing keys, the end bits and the final lengths
 //                  (7 bytes per record, dynamic, sized by the largest listed family: 112 KB at WIDE_MAX, of the CU's 160 KB).  The O(n^2) loops
@@ -121,116 +121,8 @@ __global__ __launch_bounds__(WIDE_NT) void k_wide_parse(FastParams P, WideParams
   }
   const uint32_t min_bq = P.min_input_bq & 0xFFu;
 
-  // ---- 1. parse: thread = record (k_deep_parse<.., .., 0>'s) ------------------------------------------------------------------------
-  for (uint32_t r = tid; r < n; r += DEEP_NT) {
-    const unsigned long long off = P.rec_off[r0 + r];
-    const uint32_t len = P.rec_len[r0 + r];
-    bool odd = false;
-    uint32_t l_seq = 0, seq_rel = 0, name_len = 0, clip = 0, hash = 0, flags = 0, ty = 0;
-    int32_t pos = 0, ref_id = 0;
-    uint32_t rx_rel = 0, rx_len = 0, cb_rel = 0, cb_len = 0;
-    bool has_mi = false, has_rx = false, has_cb = false;
-    uint32_t mi_len = 0;
-    if (len < 36u || len > 0xFFFFu || off > P.blob_len || (unsigned long long)len > P.blob_len - off) odd = true;
-    else {
-      const uint8_t* const rec = P.blob + off;
-      const uint32_t h2 = gld32(rec + 8), h3 = gld32(rec + 12);
-      const uint32_t l_name = h2 & 0xFF, n_cig = h3 & 0xFFFF;
-      l_seq = gld32(rec + 16);
-      flags = h3 >> 16;
-      const unsigned long long seq_off = 32ull + l_name + 4ull * n_cig;
-      const unsigned long long qual_off = seq_off + ((unsigned long long)l_seq + 1) / 2;
-      const unsigned long long aux_off = qual_off + l_seq;
-      const bool unm = (flags & bam::F_UNMAPPED) != 0;      // an unmapped record: a read without a CIGAR
-      if (aux_off > len || l_seq > 65535 || l_seq == 0 || l_name == 0 || n_cig != (unm ? 0u : 1u)) odd = true;
-      else {
-        name_len = l_name - 1;
-        ref_id = unm ? unmapped_ref_key(r) : (int32_t)gld32(rec); pos = (int32_t)gld32(rec + 4);
-        seq_rel = (uint32_t)seq_off;
-        if (flags & (bam::F_SECONDARY | bam::F_SUPPLEMENTARY)) odd = true;
-        if ((flags & bam::F_PAIRED) && !(flags & (bam::F_FIRST | bam::F_LAST))) odd = true;
-        if (!unm) {
-          if (pos < 0 || pos >= (1 << 30)) odd = true;
-          const uint32_t op = gld32(rec + 32 + l_name), t = op & 15;
-          if (!(t == 0 || t == 7 || t == 8) || (op >> 4) != l_seq) odd = true;
-        }
-        AuxTags ax;
-        aux_walk(rec, sTagCls, (uint32_t)aux_off, len - (uint32_t)aux_off, P, ax);
-        if (ax.oddw) odd = true;
-        const bool has_mc = (ax.got & 1u) != 0;
-        const uint32_t mc_lo = ax.pk_mc & 0xFFFF, mc_len = ax.pk_mc >> 16;
-        has_mi = (ax.got & 2u) != 0; mi_len = ax.pk_mi >> 16;
-        has_rx = (ax.got & 4u) != 0; rx_rel = ax.pk_rx & 0xFFFF; rx_len = ax.pk_rx >> 16;
-        has_cb = (ax.got & 8u) != 0; cb_rel = ax.pk_cb & 0xFFFF; cb_len = ax.pk_cb >> 16;
-        if (r == 0 && (!has_mi || P.prefix_len + 1 + mi_len >= 255)) odd = true;   // fatal in the reference (vanilla_caller.rs:1897-1908, 1795-1797)
-        if (!odd && has_mc && !(flags & (bam::F_UNMAPPED | bam::F_MATE_UNMAPPED))) {
-          // mate-overlap clip (raw-bam/overlap.rs:181-357) in closed form: this read and its mate are both one M op
-          bool simple = false;
-          int32_t ML = 0;
-          if (mc_len >= 2 && mc_len <= 8) {
-            const unsigned long long v = gld64(rec + mc_lo);
-            uint32_t k = 0, val = 0;
-            while (k < mc_len - 1) { const uint32_t ch = (uint32_t)(v >> (8 * k)) & 0xFF; if (ch < '0' || ch > '9') break; val = val * 10 + (ch - '0'); k++; }
-            if (k == mc_len - 1 && ((v >> (8 * k)) & 0xFF) == 'M' && val > 0) { simple = true; ML = (int32_t)val; }
-          }
-          const int32_t mpos = (int32_t)gld32(rec + 24);
-          if (!simple || mpos < 0 || mpos >= (1 << 30)) odd = true;
-          else {
-            int32_t cl = 0;
-            const int32_t mref = (int32_t)gld32(rec + 20);
-            const bool rv = (flags & bam::F_REVERSE) != 0, mrv = (flags & bam::F_MATE_REVERSE) != 0;
-            const int32_t L = (int32_t)l_seq, tp = pos + 1, mp = mpos + 1;
-            bool fr = (flags & bam::F_PAIRED) && !(flags & bam::F_MATE_UNMAPPED) && ref_id == mref && rv != mrv;
-            if (fr) fr = rv ? (mp < tp + (L - 1)) : (tp < mp + (ML - 1));
-            if (fr) {
-              const int32_t read_end = tp - 1 + L, mate_end = mp - 1 + ML;
-              if (rv) {
-                if (!(tp > mate_end) && !(read_end < mp)) {
-                  const int32_t fs = tp > mp ? tp : mp;
-                  int32_t rb = fs - tp; if (rb > L) rb = L;
-                  int32_t mb = fs - mp; if (mb > ML) mb = ML;
-                  cl = rb > mb ? rb - mb : 0;
-                }
-              } else {
-                if (!(read_end < mp) && !(mate_end < tp)) {
-                  const int32_t ls = read_end < mate_end ? read_end : mate_end;
-                  int32_t ra = ls - tp + 1; if (ra > L) ra = L;
-                  int32_t ma = ls - mp + 1; if (ma > ML) ma = ML;
-                  const int32_t rp = L - ra, mq = ML - ma;
-                  cl = rp > mq ? rp - mq : 0;
-                }
-              }
-            }
-            clip = (uint32_t)cl;
-          }
-        }
-        if (!odd) {
-          // 30-bit name hash for mate pairing: a filter only, candidates are compared byte by byte below
-          uint32_t h = name_len, i = 0;
-          for (; i + 8 <= name_len; i += 8) { h = __builtin_rotateleft32(h, 5) ^ gld32(rec + 32 + i); h = __builtin_rotateleft32(h, 11) + gld32(rec + 36 + i); }
-          if (i < name_len) {
-            uint32_t w0, w1;
-            if (name_len >= 8) { w0 = gld32(rec + 24 + name_len); w1 = gld32(rec + 28 + name_len); }
-            else { const unsigned long long v = gld64(rec + 32) & ((1ULL << (8 * name_len)) - 1ULL); w0 = (uint32_t)v; w1 = (uint32_t)(v >> 32); }
-            h = __builtin_rotateleft32(h, 5) ^ w0; h = __builtin_rotateleft32(h, 11) + w1;
-          }
-          hash = h ^ (h >> 15) ^ (h << 7);
-          if (rec[(uint32_t)qual_off] == 0xFF) odd = true;                 // absent qualities (:1119-1124): the first one decides here
-          if (has_rx && rx_len > 255u) odd = true;
-        }
-        ty = !(flags & bam::F_PAIRED) ? 0u : (flags & bam::F_FIRST) ? 1u : 2u;
-      }
-    }
-    if (odd) C.bad = 1;
-    else if (flags & bam::F_UNMAPPED) atomicOr(&C.bad, 2u << ty);    // bits 1 - 3: the end holds an unmapped record
-    const uint32_t pt = odd ? 0u : (flags & bam::F_FIRST) ? 1u : (flags & bam::F_LAST) ? 2u : 0u;   // pair-map type (overlapping.rs:627-684)
-    S.off[r] = off; S.key[r] = (hash << 2) | pt; S.pos[r] = pos; S.ref_id[r] = ref_id;
-    S.l_seq[r] = (uint16_t)l_seq; S.seq_rel[r] = (uint16_t)seq_rel; S.name_len[r] = (uint16_t)name_len; S.clip[r] = (uint16_t)clip; S.final_len[r] = 0;
-    S.wo[r] = 0; S.mo[r] = 0; S.wc[r] = 0; S.partner[r] = 0xFFFFFFFFu;
-    S.rx_rel[r] = (uint16_t)rx_rel; S.cb_rel[r] = (uint16_t)cb_rel; S.rx_len[r] = (uint8_t)rx_len; S.cb_len[r] = (uint8_t)cb_len;
-    S.bits[r] = (uint8_t)(ty | ((flags & bam::F_REVERSE) ? 4u : 0u) | (has_rx ? 8u : 0u) | (has_cb ? 16u : 0u) | ((flags & bam::F_LAST) ? 32u : 0u) |
-                         ((flags & bam::F_UNMAPPED) ? 64u : 0u));
-  }
+  // ---- 1. parse: thread = record (deep_parse_records, simplex_deep.inc) ---------------------------------------------------------------
+  deep_parse_records<0>(P, S, C, r0, n, tid, DEEP_NT, sTagCls, true);
   __syncthreads();
   if (C.bad & 1u) { leave(); return; }
   if (C.bad >> 1) {
