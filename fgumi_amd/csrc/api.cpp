@@ -1525,6 +1525,17 @@ void fgx_debug_last_packed_rows(const fgx_caller* c, uint64_t* out2) {
   out2[0] = out2[1] = 0;
   if (c && c->fast) { out2[0] = c->fast->fp.last_packed_clean; out2[1] = c->fast->fp.last_packed_general; }
 }
+// k_call_full's answers in the last device batch (fastpath.h, FullResult): out4[0] column answers that went to the pair writer through the result array,
+// [1] column answers scattered into the scratch planes, [2] families whose answers the pair writer applies (families without items included), [3] families
+// the pair writer takes but whose items a list's end cuts in two: not in one piece (their answers are scattered)
+void fgx_debug_last_full_results(const fgx_caller* c, uint64_t* out4) {
+  if (!out4) return;
+  for (int i = 0; i < 4; i++) out4[i] = (c && c->fast) ? c->fast->fp.last_full_results[i] : 0;
+}
+// ... and the families the pair writer takes but that hold more than the 64 results a wavefront loads (scattered too)
+uint64_t fgx_debug_last_full_results_over(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_full_results[4] : 0; }
+// the rule "a family's items lie in one piece" (full_range_whole), for tests: `items` slots reserved at `base` of a list of `cap`
+int fgx_debug_full_range_whole(uint32_t base, uint32_t items, uint32_t cap) { return full_range_whole(base, items, cap) ? 1 : 0; }
 // the launch chain of the last device batch: out2[0] kernel launches of fastpath.hip's run_once (the scans of the library not counted), out2[1] host synchronisations in it
 void fgx_debug_last_chain(const fgx_caller* c, uint32_t* out2) { if (out2) { out2[0] = (c && c->fast) ? c->fast->fp.last_launches : 0u; out2[1] = (c && c->fast) ? c->fast->fp.last_host_syncs : 0u; } }
 uint32_t fgx_debug_last_routed(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_routed : 0u; }

@@ -3,6 +3,13 @@
 #include <algorithm>
 #include "engine.h"
 
+// (small rules shared by kernels and host code)
+#if defined(__HIPCC__)
+#define FP_HD __host__ __device__ __forceinline__
+#else
+#define FP_HD inline
+#endif
+
 namespace fgx {
 
 constexpr int FAST_RX_CAP = 48;   // longest RX value handled on the device (longer → general path)
@@ -84,6 +91,51 @@ constexpr uint32_t FULL_ITEM_OBS = 0x80000000u;
 // with m = chains & 0xFF, then continuation items — chains == FULL_ITEM_CONT, observations 16 .. in `ll` again — which k_call_full's own
 // threads skip.  (A family's items stay in one list when it holds such a column: k_split_cols pads a list's tail with continuation items.)
 constexpr uint32_t FULL_ITEM_CONT = 0x40000000u;
+
+// ---- k_call_full's answers for the pair writer (FGX_FULL_RESULTS, on by default) ---------------------------------------------------------
+// The answer to an item is six bytes that ONE kernel reads: k_emit, which holds the family's columns in registers a moment later.  For a
+// family the packed build of k_split_cols finished and emit_pair will write (full_results_family below), k_call_full leaves the answer in
+// slot `list * full_cap + i` of an array beside the item pool — one coalesced 8-byte store — instead of four sub-dword stores into scratch
+// planes whose lines left the cache milliseconds ago, and emit_pair patches the family's few answers into its registers.
+//   k_split_cols (packed build, scratch path) writes the family's index + 1 into the `obs` word of its observation and continuation items
+//                and {first slot, items, in one piece} into the 64-bit word `col_off` of the family's FRAGMENT EndDesc (slot 3g: no record
+//                of a pair family, copied to LDS by k_emit with the other two);
+//   k_split_finish decides with full_results_family and writes the family's byte of `full_flag` (cleared per batch);
+//   k_call_full reads that byte through the item's family index; every other item is scattered into the planes as before;
+//   k_emit     reads the same byte and, when set, lets emit_pair load and apply the family's results.
+struct FullResult {
+  uint32_t w0;              // low 16 bits of the scratch column index | code << 16 | quality << 24 (code FULL_RESULT_NONE: a continuation item's slot)
+  uint32_t w1;              // errors (<= 32767) | depth << 16
+};
+static_assert(sizeof(FullResult) == 8, "a result is one 8-byte store");
+constexpr uint32_t FULL_RESULT_NONE = 0xFFu;
+constexpr uint32_t FULL_RESULT_MAX_ITEMS = 64;   // a lane of the writer's wavefront per result
+// the default of the switch FGX_FULL_RESULTS (1: on unless FGX_FULL_RESULTS=0; 0: on only with FGX_FULL_RESULTS=1)
+#ifndef FGX_FULL_RESULTS_DEFAULT
+#define FGX_FULL_RESULTS_DEFAULT 1
+#endif
+// counters of the path (fgx_debug_last_full_results), spread over STAT_SLOTS slots of FULL_STATS_STRIDE words: [0] column answers through the array, [1] column answers
+// scattered, [2] families the writer applies, [3] families refused because their items are not in one piece, [4] families refused because they hold more than 64 items
+constexpr int FULL_STATS_N = 5, FULL_STATS_STRIDE = 8;
+// the family's word in its fragment EndDesc: first slot | items << 32 | (in one piece) << 48
+FP_HD uint64_t full_range_word(uint32_t first, uint32_t items, bool whole) {
+  return (uint64_t)first | ((uint64_t)(items < 0xFFFFu ? items : 0xFFFFu) << 32) | ((uint64_t)(whole ? 1u : 0u) << 48);
+}
+// Where a family's items went when `items` of them were reserved at `base` of a list of `cap` slots (s2_cols_family phase 7): in one piece
+// iff the reservation lies inside the list.  (A family with a column of several items never cuts its range: it moves to a list that holds it all.)
+FP_HD bool full_range_whole(uint32_t base, uint32_t items, uint32_t cap) { return base < cap && items <= cap - base; }
+// emit_pair's condition, as a function of the descriptors' fields: k_split_finish and emit_pair call this one function.  dcol: first scratch
+// column of R2 minus that of R1; dout: output offset of R2 minus that of R1 (both as unsigned differences: a negative one is huge).
+FP_HD bool emit_pair_takes(uint32_t Lc1, uint32_t Lc2, uint32_t name_len, uint32_t rg_len, uint32_t mi_len, uint32_t cbl1, uint32_t cbl2,
+                                                uint32_t rxl1, uint32_t rxl2, bool same_first, uint64_t dcol, uint64_t dout) {
+  return Lc1 >= 8u && Lc1 <= 256u && Lc2 >= 8u && Lc2 <= 256u && name_len + 1u <= 32u && rg_len + 4u <= 32u && mi_len + 4u <= 32u &&
+         cbl1 + 4u <= 32u && cbl2 + 4u <= 32u && rxl1 + 4u <= 32u && rxl2 + 4u <= 32u && rxl1 <= (uint32_t)FAST_RX_CAP && rxl2 <= (uint32_t)FAST_RX_CAP &&
+         same_first && dcol < (1ull << 30) && dout - 1ull < (1ull << 30) - 1ull;
+}
+// "the writer applies": a pair family of the packed build whose items lie in one piece of at most 64 slots and whose pair emit_pair takes
+FP_HD bool full_results_family(bool packed, bool pair, bool whole, uint32_t items, bool pair_taken) {
+  return packed && pair && whole && items <= FULL_RESULT_MAX_ITEMS && pair_taken;
+}
 
 // ---- split simplex pipeline (simplex_split.inc): k_split_parse leaves one SplitRec per record and one SplitFam per family;
 // k_split_cols (one wavefront per family) reads them instead of parsing, pairing and walking tags itself --------------------------
@@ -178,6 +230,9 @@ struct FastParams {
   uint32_t s2_packed;              // k_split_cols: 1 = ends of at least s2_nsafe rows try the packed pass first (round 5; FGX_S2_PACKED=0: measurements); | 2: debug counters; | 4: the clean test (FGX_S2_CLEAN_ROWS=0: off)
   uint32_t s2_nsafe;               // k_split_cols: unanimous_cap_depth(tables, min_input_bq) — agreeing observations from which a column is the cap for certain (gate_core.h)
   FullItem* full_items; uint32_t* full_count; uint32_t full_cap;   // N_LISTS append lists of `full_cap` items each
+  uint32_t full_results;           // 1: k_call_full's answers go to the pair writer through a result array (FullResult above; FGX_FULL_RESULTS=0: off)
+  uint8_t* full_flag;              // per family: the writer applies its results (k_split_finish; cleared per batch)
+  unsigned long long* full_stats;  // STAT_SLOTS x FULL_STATS_STRIDE words: the counters of the path (FULL_STATS_N above)
   // methylation-aware mode on the streaming kernels (simplex_deep.inc; meth_mode = FGX_METHYLATION_*, 0: off): the genome of fgx_set_reference
   // (contig i = [contig_off[i], + contig_len[i])), and per scratch column: the reference shows a cytosine of the call's strand | unconverted |
   // converted source bases (methylation.rs:193-242)
@@ -200,6 +255,7 @@ struct EmitParams {
   const char* prefix; uint32_t prefix_len; const char* rg; uint32_t rg_len;
   uint8_t per_base_tags; char tag0, tag1, cell0, cell1;
   const uint32_t* fam_list; uint32_t n_fam;   // non-null: a wavefront per LISTED family (direct records: the families that left the split pipeline)
+  const FullResult* full_res; const uint8_t* full_flag;   // k_call_full's answers for emit_pair (null: none; fastpath.h, FullResult)
 };
 
 struct DuplexEmitParams {
@@ -239,6 +295,8 @@ struct FastPath {
   uint32_t lds_tile_bytes = 12288;        // first launch: tiles of the common small families
   uint32_t lds_tile_bytes_large = 65536;  // workgroup-per-family kernel: raw records + unpacked base / quality tiles of one big family (2 workgroups per CU)
   DevBuf d_retry, d_bound, d_colbase, d_statslots, d_full_items, d_full_count, d_obs, d_obs_all, d_retry2, d_retry_old;
+  DevBuf d_full_res, d_full_flag;         // k_call_full's result array (a slot per slot of d_full_items) and the per-family flags
+  uint64_t last_full_results[FULL_STATS_N] = {0, 0, 0, 0, 0};   // the last batch: items answered through the array, items scattered, families the writer applied, families refused as not in one piece
   DevBuf d_w2img;                         // W2Lds image, built from the caller's tables at the first batch
   DevBuf d_famdesc;                       // k_col_bound's family descriptors
   DevBuf d_fwimg;                         // FwLds image (k_family_wave)

@@ -2629,6 +2629,8 @@ struct FullParams {
   uint16_t* col_depth; uint32_t min_input_bq;   // observation items (k_split_cols): the column's depth is counted here
   // direct records (FullItem.dest & FULL_DEST_DIRECT): the column is patched in the record k_split_cols wrote
   uint8_t* out; const SlotDesc* slot_desc; uint32_t* slot_err; uint32_t rg_len, per_base_tags;
+  // the answers the pair writer applies (fastpath.h, FullResult): slot list * cap + i of `res` for the items of the families flagged in `flag` (null: every answer is scattered)
+  FullResult* res; const uint8_t* flag; uint32_t n_flag; unsigned long long* stats;
 };
 
 // A column of a directly written record (fastpath.h: SlotDesc): the sequence nibble is OR-ed into the word that holds its byte (k_split_cols
@@ -2703,6 +2705,7 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
   __shared__ unsigned long long sDest[256];
   __shared__ uint32_t sObs[256];         // observation counts, a byte each, in the order of sLL; bit 31 of sKind: an observation item (depth counted here)
   __shared__ uint32_t sKind[256];
+  __shared__ uint32_t sSlot[256];        // where the answer goes: the item's slot of the result array, or NO_SLOT (scattered into the planes)
   __shared__ uint32_t sCnt;
   __shared__ double sTab[94][2];         // {correct, error_per_alt} by quality: an observation item reads a pair per observation (from global memory that is a dependent ~1 us chain per item)
   const uint32_t list = blockIdx.y;
@@ -2714,7 +2717,9 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
   __syncthreads();
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   // what a decided column leaves (vanilla_caller.rs:1711-1748); `is_obs`: an observation item — its depth is written too
-  auto finish = [&](uint64_t dest, int bi, uint8_t q, uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3, bool is_obs) {
+  constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
+  uint32_t n_arr = 0, n_scat = 0;                  // (fgx_debug_last_full_results) column answers of this thread: through the result array / scattered
+  auto finish = [&](uint64_t dest, int bi, uint8_t q, uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3, bool is_obs, uint32_t slot) {
     const uint32_t depth = o0 + o1 + o2 + o3;
     const uint32_t err = depth - (bi == 0 ? o0 : bi == 1 ? o1 : bi == 2 ? o2 : bi == 3 ? o3 : 0u);
     const uint8_t code = bi >= 0 ? (uint8_t)(1u << bi) : 15;
@@ -2723,17 +2728,30 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
     else if (q < P.min_cons_bq) { ob = 15; oq = FGX_MIN_PHRED; }
     else { ob = code; oq = q; }
     if (dest & FULL_DEST_DIRECT) { full_patch_direct(P, dest, ob, oq, err, depth, is_obs); return; }
+    if (slot != NO_SLOT) {   // the family's writer applies it (observation items only: the depth travels too)
+      FullResult r;
+      r.w0 = ((uint32_t)dest & 0xFFFFu) | ((uint32_t)ob << 16) | ((uint32_t)oq << 24); r.w1 = (err < 32767u ? err : 32767u) | (depth << 16);
+      P.res[slot] = r;
+      n_arr++;
+      return;
+    }
+    n_scat++;
     P.col_code[dest] = ob; P.col_qual[dest] = oq; P.col_err[dest] = (uint16_t)(err < 32767u ? err : 32767u);
     if (is_obs) P.col_depth[dest] = (uint16_t)depth;
   };
-  auto push = [&](uint64_t dest, const double* ll, uint32_t obs, uint32_t kind) {
+  auto push = [&](uint64_t dest, const double* ll, uint32_t obs, uint32_t kind, uint32_t slot) {
     const uint32_t k = atomicAdd(&sCnt, 1u);
     sLL[k][0] = ll[0]; sLL[k][1] = ll[1]; sLL[k][2] = ll[2]; sLL[k][3] = ll[3];
-    sDest[k] = dest; sObs[k] = obs; sKind[k] = kind;
+    sDest[k] = dest; sObs[k] = obs; sKind[k] = kind; sSlot[k] = slot;
   };
   if (i < cnt) {
     FullItem it = P.items[(size_t)list * P.cap + i];
-    if (it.chains == FULL_ITEM_CONT) { /* observations 16 .. of the column whose head item sits before it (or padding) */ }
+    // an observation or continuation item of the packed build carries its family's index + 1 in `obs`: does the pair writer apply that family's answers?
+    const bool obs_kind = it.chains == FULL_ITEM_CONT || (it.chains & FULL_ITEM_OBS) != 0;
+    const uint32_t slot = (P.flag && obs_kind && it.obs != 0u && it.obs <= P.n_flag && P.flag[it.obs - 1u]) ? list * P.cap + i : NO_SLOT;
+    if (it.chains == FULL_ITEM_CONT) {   // observations 16 .. of the column whose head item sits before it (or padding): no answer of its own
+      if (slot != NO_SLOT) { FullResult r; r.w0 = FULL_RESULT_NONE << 16; r.w1 = 0u; P.res[slot] = r; }
+    }
     else if (it.chains & FULL_ITEM_OBS) {
       // a column k_split_cols did not answer: its observations in file order, 16 bits each — the four-lane Kahan sum of
       // ConsensusBaseBuilder::add (base_builder.rs:836-868), then the call.  More than 16 of them: the following items hold the rest.
@@ -2756,8 +2774,8 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
       }
       int bi = -1;
       uint8_t q = FGX_MIN_PHRED;
-      if (acc.contributions() == 0 || unanimous_fast_path(TT, acc.s, acc.obs, &bi, &q)) finish(it.dest, bi, q, acc.obs[0], acc.obs[1], acc.obs[2], acc.obs[3], true);
-      else push(it.dest, acc.s, acc.obs[0] | (acc.obs[1] << 8) | (acc.obs[2] << 16) | (acc.obs[3] << 24), 0x80000000u);
+      if (acc.contributions() == 0 || unanimous_fast_path(TT, acc.s, acc.obs, &bi, &q)) finish(it.dest, bi, q, acc.obs[0], acc.obs[1], acc.obs[2], acc.obs[3], true, slot);
+      else push(it.dest, acc.s, acc.obs[0] | (acc.obs[1] << 8) | (acc.obs[2] << 16) | (acc.obs[3] << 24), 0x80000000u, slot);
     } else {
       if (it.chains) {   // chains by order of appearance (k_simplex_wave2 / k_simplex_seg): the bases are sorted out here, once per item
         const uint32_t b1 = it.chains & 15, b2 = (it.chains >> 4) & 15, b3 = (it.chains >> 8) & 15;
@@ -2772,7 +2790,7 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
         }
         it.obs = packed;
       }
-      push(it.dest, it.ll, it.obs, 0u);       // (the kernels that send these have run their gates already)
+      push(it.dest, it.ll, it.obs, 0u, NO_SLOT);       // (the kernels that send these have run their gates already)
     }
   }
   __syncthreads();
@@ -2790,7 +2808,15 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
     if (is_rx) {
       const uint64_t d = dest & ~(1ull << 63);
       P.rx_base[(size_t)(d >> 8) * P.rx_stride + (d & 0xFF)] = bi >= 0 ? "ACGT"[bi] : 'N';
-    } else finish(dest, bi, q, ob & 0xFF, (ob >> 8) & 0xFF, (ob >> 16) & 0xFF, ob >> 24, (sKind[k] >> 31) != 0);
+    } else finish(dest, bi, q, ob & 0xFF, (ob >> 8) & 0xFF, (ob >> 16) & 0xFF, ob >> 24, (sKind[k] >> 31) != 0, sSlot[k]);
+  }
+  if (P.stats) {   // one atomic per wavefront and counter, spread over the slots
+    const uint32_t t_arr = wave_sum(n_arr), t_scat = wave_sum(n_scat);
+    if ((threadIdx.x & 63) == 0) {
+      unsigned long long* fs = P.stats + (size_t)((blockIdx.x * 4 + blockIdx.y + (threadIdx.x >> 6)) & (STAT_SLOTS - 1)) * FULL_STATS_STRIDE;
+      if (t_arr) atomicAdd(&fs[0], (unsigned long long)t_arr);
+      if (t_scat) atomicAdd(&fs[1], (unsigned long long)t_scat);
+    }
   }
 }
 
@@ -2855,8 +2881,13 @@ __global__ void k_col_bound(const uint32_t* __restrict__ grp_first, const uint32
   fam_desc[g] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), span, b - a);
 }
 
-__global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, unsigned long long* __restrict__ out) {
+__global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, unsigned long long* __restrict__ out, const unsigned long long* __restrict__ full_stats, uint32_t full_out) {
   uint32_t k = threadIdx.x;   // one thread per counter; the slots' entries 28 .. 31 are diagnostics (k_split_finish: families per build) and go to out[40 ..]
+  if (k >= 32 && k < 32 + FULL_STATS_N) {    // the counters of the result array (fastpath.h, FullResult): slots of their own
+    unsigned long long v = 0;
+    for (int i = 0; i < STAT_SLOTS; i++) v += full_stats[(size_t)i * FULL_STATS_STRIDE + (k - 32)];
+    out[full_out + (k - 32)] = v;
+  }
   if (k >= 32) return;
   unsigned long long v = 0;
   for (int i = 0; i < STAT_SLOTS; i++) v += slots[(size_t)i * 32 + k];
@@ -2876,7 +2907,7 @@ __global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, uns
 
 void FastPath::release() {
   for (DevBuf* b : {&d_ends, &d_sizes, &d_offsets, &d_code, &d_qual, &d_depth, &d_err, &d_misc, &d_deferred, &d_out, &d_scan_tmp, &d_strings, &d_obs, &d_obs_all, &d_retry2,
-                    &d_retry, &d_bound, &d_colbase, &d_statslots, &d_full_items, &d_full_count, &d_retry_old, &d_w2img, &d_famdesc, &d_fwimg,
+                    &d_retry, &d_bound, &d_colbase, &d_statslots, &d_full_items, &d_full_count, &d_full_res, &d_full_flag, &d_retry_old, &d_w2img, &d_famdesc, &d_fwimg,
                     &d_split_rec, &d_split_fam, &d_split_out, &d_route, &d_s2img, &d_dir_size, &d_dir_off, &d_dir_base, &d_slot_desc, &d_slot_err, &d_out2, &d_scan_tmp2, &d_big, &d_deep_sizes, &d_deep_row0, &d_deep_rows, &d_deep_fams, &d_deep_out, &d_deep_out2, &d_wide_scratch, &d_wide_pass, &d_wide_pass0, &d_wide_depth, &d_mflag, &d_mu, &d_mt, &d_mslot, &d_mcontigs})
     b->free_();
   for (int i = 0; i < 4; i++) if (ev[i]) { (void)hipEventDestroy(ev[i]); ev[i] = nullptr; }
@@ -2905,8 +2936,9 @@ enum MiscWord : uint32_t {
   MISC_N_DEEP = 38,          // families a pass of the streaming kernels hands on
   MISC_BUILD_FAMILIES = 40,  // [40, 44): the slots' diagnostics (k_reduce_stats): families finished by k_split_cols's packed build, by its classic builds, by the packed build's clean / general row loop
   MISC_N_SLOW = 44,          // duplex / CODEC: records the fast writer leaves to the per-field kernel
-  MISC_READ_BACK = 46,       // words the end of a batch copies to the host
-  MISC_WORDS = 48
+  MISC_FULL_RESULTS = 46,    // [46, 51): items answered through the result array, items scattered, families the writer applies, families refused as not in one piece, families refused for more than 64 items
+  MISC_READ_BACK = 51,       // words the end of a batch copies to the host
+  MISC_WORDS = 52
 };
 constexpr uint32_t MISC_SPLIT_WINDOW = MISC_N_BIG - MISC_N_RETRY + 1;   // retry, route and big counts of a split stage come back as ONE copy
 static_assert(FGX_STATS_LEN <= MISC_COLS_USED && MISC_BUILD_FAMILIES == 40 && MISC_BUILD_FAMILIES + (32 - FGX_STATS_LEN) <= MISC_N_SLOW,
@@ -2931,6 +2963,7 @@ struct ProcessSwitches {   // read once per process, at the first batch
   const int nosum = env_int(fgx_knob("FGX_S2_NOSUM"), 1);                // 0: every end through the f32 sums
   const int packed = env_int(getenv("FGX_S2_PACKED"), 1);                // 0: the 64-column passes only
   const bool clean_rows = env_not0(getenv("FGX_S2_CLEAN_ROWS"));         // 0: the packed pass reads the qualities of every family (no clean test)
+  const bool full_results = FGX_FULL_RESULTS_DEFAULT ? env_not0(getenv("FGX_FULL_RESULTS")) : env_is1(getenv("FGX_FULL_RESULTS"));   // k_call_full's answers through the result array (fastpath.h, FullResult)
   const int s2_debug = env_int(fgx_knob("FGX_S2_DEBUG"), 0);
   const int pace = env_int(fgx_knob("FGX_S2_PACE"), 1);                  // 0: all record kernels up front
   const uint32_t s2_bytes = env_in(fgx_knob("FGX_S2_BYTES"), 2048, 32768, 0) & ~15u, s2_wpb = env_in(fgx_knob("FGX_S2_WPB"), 1, 4, 0);
@@ -3033,6 +3066,9 @@ struct Batch {
   // ---- sizes, buffers ----
   const uint32_t n_slots = 3 * n_grp;       // simplex: Fragment, R1, R2 of each family; duplex: slot 0 unused, R1, R2
   uint64_t col_cap = 0, dir_cap = 0; uint32_t full_cap = 0;
+  bool full_results = false;                // k_call_full's answers of this batch go to the pair writer through fp.d_full_res (fastpath.h, FullResult)
+  static constexpr size_t FULL_STATS_BYTES = (size_t)STAT_SLOTS * FULL_STATS_STRIDE * 8;
+  FullResult* full_res() const { return (FullResult*)((uint8_t*)fp.d_full_res.p + FULL_STATS_BYTES); }
   unsigned long long* misc = nullptr;
   uint32_t* cnt(MiscWord w) const { return (uint32_t*)(misc + w); }
   FastParams P;                             // the kernels' parameters; a launch works on a copy with its list and slice
@@ -3089,7 +3125,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
-    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
+    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
     fp.d_offsets.reserve(((size_t)n_slots + 1) * 8);
@@ -3227,6 +3263,18 @@ struct Batch {
     fp.d_full_count.reserve((size_t)N_LISTS * 4);
     hip_check(hipMemsetAsync(fp.d_full_count.p, 0, (size_t)N_LISTS * 4, s), "memset");
     P.full_items = fp.d_full_items.as<FullItem>(); P.full_count = fp.d_full_count.as<uint32_t>(); P.full_cap = full_cap;
+    // the answers the pair writer applies (fastpath.h, FullResult): a slot per slot of the pool, a flag per family, four slot-spread counters.
+    // Simplex on the scratch path only, and a pool whose slots a 32-bit index reaches.
+    // (never without its only reader: a build without the pair writer, FGX_EMIT_PAIR=0, reads the planes)
+    full_results = ps.full_results && FGX_EMIT_PAIR != 0 && !duplex && !codec && !direct && !meth_dev && (uint64_t)full_cap * N_LISTS <= 0xFFFFFFFFull;
+    fp.d_full_res.reserve(FULL_STATS_BYTES + (full_results ? (size_t)full_cap * N_LISTS * sizeof(FullResult) : 0));   // (the counters in front of the slots)
+    hip_check(hipMemsetAsync(fp.d_full_res.p, 0, FULL_STATS_BYTES, s), "memset");
+    P.full_stats = fp.d_full_res.as<unsigned long long>();
+    if (full_results) {
+      fp.d_full_flag.reserve((size_t)n_grp + 16);
+      hip_check(hipMemsetAsync(fp.d_full_flag.p, 0, (size_t)n_grp, s), "memset");
+      P.full_results = 1; P.full_flag = fp.d_full_flag.as<uint8_t>();
+    }
     P.lds_wave_bytes = sw.wave_bytes ? sw.wave_bytes : duplex ? fp.lds_wave_bytes_duplex : codec ? fp.lds_wave_bytes_codec : fp.lds_wave_bytes;
     P.lds_tile_bytes = fp.lds_tile_bytes_large;
     if (!fp.lds_attr_set) {
@@ -3663,6 +3711,8 @@ struct Batch {
       F.out = P.out; F.slot_desc = P.slot_desc; F.slot_err = P.slot_err; F.rg_len = P.rg_len; F.per_base_tags = P.per_base_tags;
       F.rx_base = fp.d_ends.as<char>() + (duplex ? offsetof(DuplexDesc, rx) : codec ? offsetof(CodecDesc, rx) : offsetof(EndDesc, rx));
       F.rx_stride = duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc);
+      if (full_results) { F.res = full_res(); F.flag = P.full_flag; F.n_flag = n_grp; }
+      F.stats = P.full_stats;
       FGX_LAUNCH(k_call_full, dim3((mx + 255) / 256, N_LISTS), dim3(256), 0, s, F);
     }
     // the methylation tags' share of the record sizes: the consensus bases are final now
@@ -3754,6 +3804,7 @@ struct Batch {
       EmitParams E;
       emit_params(E, fp.d_ends.as<EndDesc>(), out_ptr);
       E.col_depth = P.col_depth; E.tag0 = P.tag0; E.tag1 = P.tag1;
+      if (full_results) { E.full_res = full_res(); E.full_flag = P.full_flag; }
       if (!direct) FGX_LAUNCH(k_emit, wave_per_family, dim3(256), 0, s, E);   // one wavefront per family (slots 3g .. 3g + 2)
       else {
         // the merge: the families that left the split pipeline are written by k_emit from their descriptors, the directly written ones move
@@ -3772,7 +3823,7 @@ struct Batch {
     hip_check(hipEventRecord(c->ev1, s), "event");
     unsigned long long h_misc[MISC_READ_BACK];
     auto read_counters = [&] {
-      FGX_LAUNCH(k_reduce_stats, dim3(1), dim3(64), 0, s, fp.d_statslots.as<unsigned long long>(), misc);
+      FGX_LAUNCH(k_reduce_stats, dim3(1), dim3(64), 0, s, fp.d_statslots.as<unsigned long long>(), misc, (const unsigned long long*)P.full_stats, (uint32_t)MISC_FULL_RESULTS);
       hip_check(hipMemcpyAsync(h_misc, misc, sizeof(h_misc), hipMemcpyDeviceToHost, s), "D2H");
       sync();
     };
@@ -3801,6 +3852,7 @@ struct Batch {
     res->ms_kernels = ms; res->ms_k_family = msf; res->ms_k_emit = mse;
     fp.last_packed_families = h_misc[MISC_BUILD_FAMILIES]; fp.last_classic_families = h_misc[MISC_BUILD_FAMILIES + 1];
     fp.last_packed_clean = h_misc[MISC_BUILD_FAMILIES + 2]; fp.last_packed_general = h_misc[MISC_BUILD_FAMILIES + 3];
+    for (int i = 0; i < FULL_STATS_N; i++) fp.last_full_results[i] = h_misc[MISC_FULL_RESULTS + i];
     res->cols_used = h_misc[MISC_COLS_USED];
     res->full_items = n_full;
   }

@@ -365,7 +365,15 @@ __device__ __forceinline__ void emit_store(const EmitParams& P, const EndDesc& D
 // with the record (an overlapping store of the same values; its duplicate columns are masked out of the sums) —, the small fields are a lane per
 // byte of the half's record, and every address is ONE scalar base (record R1, the scratch columns of R1) + a 32-bit lane offset: R2 follows R1
 // in the output, and its columns follow R1's in the scratch.  cD / cM / cE: the four reductions stop at the half (five DPP steps).
-// Taken when both records are there, 8 <= Lc <= 256 and every string field fits 32 lanes; returns false (nothing touched) otherwise.
+// Taken when both records are there, 8 <= Lc <= 256 and every string field fits 32 lanes (emit_pair_takes, fastpath.h: k_split_finish asks the same
+// function); returns false (nothing touched) otherwise.
+// (round 7) fr_cnt != 0: k_call_full left this family's answers in slots [fr_first, fr_first + fr_cnt) of P.full_res instead of the scratch planes
+// (fastpath.h, FullResult).  Lane j < fr_cnt loads result j with the column loads.  The lanes put their groups into the wavefront's 3 KB of `patch`
+// (LDS, a lane's group at the lane's index: aligned), the lane of a result overwrites its column's code, quality, depth and errors there — in the
+// lane whose group holds the column and, where the half's pulled-back last group holds it too, in that lane as well; the code groups start at cs,
+// the others at c0 —, and every lane takes its groups back before the reductions.  One round trip through LDS whatever the number of results, and
+// nothing on the vector ALU, which this kernel is short of: a broadcast loop costs ~40 vector instructions per result against the kernel's 394 per family.
+constexpr uint32_t EMIT_PATCH_BYTES = 64u * (8u + 8u + 16u + 16u);
 #ifndef FGX_EMIT_PAIR
 #define FGX_EMIT_PAIR 1
 #endif
@@ -378,7 +386,8 @@ __device__ __forceinline__ uint32_t em_sum2(uint32_t pair, uint32_t acc) { em_u1
 #define FGX_HALF_REDUCE(v, idn, OP) do { \
     v = OP(v, wave_dpp<0xB1, 0xF>(idn, v)); v = OP(v, wave_dpp<0x4E, 0xF>(idn, v)); v = OP(v, wave_dpp<0x141, 0xF>(idn, v)); v = OP(v, wave_dpp<0x140, 0xF>(idn, v)); \
     v = OP(v, wave_dpp<0x142, 0xA>(idn, v)); } while (0)
-__device__ __forceinline__ bool emit_pair(const EmitParams& P, const EndDesc* D /* [3]: slots F, R1, R2 in LDS */, uint64_t oo1, uint64_t oo2, uint32_t lane) {
+__device__ __forceinline__ bool emit_pair(const EmitParams& P, const EndDesc* D /* [3]: slots F, R1, R2 in LDS */, uint64_t oo1, uint64_t oo2, uint32_t lane,
+                                          uint8_t* const patch, const uint32_t fr_first, const uint32_t fr_cnt) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const EndDesc& D1 = D[1];
   const EndDesc& D2 = D[2];
@@ -389,10 +398,8 @@ __device__ __forceinline__ bool emit_pair(const EmitParams& P, const EndDesc* D 
   const bool hcb1 = uni(D1.has_cb) != 0, hcb2 = uni(D2.has_cb) != 0, hrx1 = uni(D1.has_rx) != 0, hrx2 = uni(D2.has_rx) != 0;
   const uint32_t cbl1 = hcb1 ? uni(D1.cb_len) : 0u, cbl2 = hcb2 ? uni(D2.cb_len) : 0u, rxl1 = hrx1 ? uni(D1.rx_len) : 0u, rxl2 = hrx2 ? uni(D2.rx_len) : 0u;
   const uint32_t name_len = P.prefix_len + 1u + mi_len, rg_len = P.rg_len;
-  const bool ok = Lc1 >= 8u && Lc1 <= 256u && Lc2 >= 8u && Lc2 <= 256u && name_len + 1u <= 32u && rg_len + 4u <= 32u && mi_len + 4u <= 32u &&
-                  cbl1 + 4u <= 32u && cbl2 + 4u <= 32u && rxl1 + 4u <= 32u && rxl2 + 4u <= 32u && rxl1 <= (uint32_t)FAST_RX_CAP && rxl2 <= (uint32_t)FAST_RX_CAP &&
-                  uniform_u64(D2.first_off) == first_off && uni(D2.mi_len) == mi_len && uni(D2.mi_off) == mi_off &&
-                  col2 >= col1 && col2 - col1 < (1ull << 30) && oo2 > oo1 && oo2 - oo1 < (1ull << 30);
+  const bool ok = emit_pair_takes(Lc1, Lc2, name_len, rg_len, mi_len, cbl1, cbl2, rxl1, rxl2,
+                                  uniform_u64(D2.first_off) == first_off && uni(D2.mi_len) == mi_len && uni(D2.mi_off) == mi_off, col2 - col1, oo2 - oo1);
   if (!ok) return false;
   const uint32_t l = lane & 31u;
   const bool hb = lane >= 32u;
@@ -411,11 +418,14 @@ __device__ __forceinline__ bool emit_pair(const EmitParams& P, const EndDesc* D 
   const uint8_t* const cq = P.col_qual + col1;
   const uint8_t* const cdb = (const uint8_t*)(P.col_depth + col1);
   const uint8_t* const ceb = (const uint8_t*)(P.col_err + col1);
-  const uint2 cw = gld64u(code + (dcol + cs));
-  const uint2 qw = gld64u(cq + (dcol + c0));
+  uint2 cw = gld64u(code + (dcol + cs));
+  uint2 qw = gld64u(cq + (dcol + c0));
   u32x4 dv, ev;
   __builtin_memcpy(&dv, cdb + 2u * (dcol + c0), 16);
   __builtin_memcpy(&ev, ceb + 2u * (dcol + c0), 16);
+  FullResult fr;
+  fr.w0 = FULL_RESULT_NONE << 16; fr.w1 = 0u;
+  if (fr_cnt != 0u && lane < fr_cnt) { const uint2 v = *(const uint2*)(P.full_res + ((size_t)fr_first + lane)); fr.w0 = v.x; fr.w1 = v.y; }
   const uint8_t* const first = P.blob + first_off;
   const uint32_t j3 = l >= 3u ? l - 3u : 0u;
   const uint32_t ni = l > P.prefix_len ? l - P.prefix_len - 1u : 0u;
@@ -430,6 +440,40 @@ __device__ __forceinline__ bool emit_pair(const EmitParams& P, const EndDesc* D 
     cbb = fk[j3 < cb_len ? j3 : 0u];
   }
   const uint8_t rxb = (uint8_t)D[hb ? 2 : 1].rx[j3 < (uint32_t)FAST_RX_CAP ? j3 : 0u];
+  // ---- k_call_full's answers for this family (wave-uniform: a family without items pays this branch) ---------------------------------------
+  if (fr_cnt != 0u) {
+    uint8_t* const pc = patch, * const pq = patch + 512u, * const pd = patch + 1024u, * const pe = patch + 2048u;
+    __builtin_memcpy(pc + 8u * lane, &cw, 8); __builtin_memcpy(pq + 8u * lane, &qw, 8);
+    __builtin_memcpy(pd + 16u * lane, &dv, 16); __builtin_memcpy(pe + 16u * lane, &ev, 16);
+    wave_sync();
+    const uint32_t r_code = (fr.w0 >> 16) & 0xFFu;
+    if (r_code != FULL_RESULT_NONE) {
+      const uint32_t d2 = (uint32_t)(col2 - col1);
+      const uint32_t rel = ((fr.w0 & 0xFFFFu) - (uint32_t)col1) & 0xFFFFu;                // the column, counted from R1's first
+      const bool h2 = rel >= d2 && rel - d2 < Lc2;                                      // (R1's columns end before R2's begin)
+      const uint32_t rh = h2 ? rel - d2 : rel, Lh = h2 ? Lc2 : Lc1, Le = (Lh + 1u) & ~1u, l0 = h2 ? 32u : 0u;
+      if (rh < Lh) {
+        const uint32_t la = rh >> 3, ll = (Lh - 1u) >> 3;                                 // the lane of the column's natural group; the half's last lane with columns
+        const uint32_t ga = min(8u * la, Lh - 8u), gl = min(8u * ll, Lh - 8u);            // first column of their groups (c0)
+        const uint32_t ea = min(8u * la, Le - 8u), el = min(8u * ll, Le - 8u);            // ... of their groups of codes (cs)
+        const uint8_t r_q = (uint8_t)(fr.w0 >> 24);
+        const uint16_t r_e = (uint16_t)(fr.w1 & 0xFFFFu), r_d = (uint16_t)(fr.w1 >> 16);
+        pc[8u * (l0 + la) + (rh - ea)] = (uint8_t)r_code;
+        pq[8u * (l0 + la) + (rh - ga)] = r_q;
+        __builtin_memcpy(pd + 16u * (l0 + la) + 2u * (rh - ga), &r_d, 2);
+        __builtin_memcpy(pe + 16u * (l0 + la) + 2u * (rh - ga), &r_e, 2);
+        if (la != ll && rh >= el) pc[8u * (l0 + ll) + (rh - el)] = (uint8_t)r_code;
+        if (la != ll && rh >= gl) {
+          pq[8u * (l0 + ll) + (rh - gl)] = r_q;
+          __builtin_memcpy(pd + 16u * (l0 + ll) + 2u * (rh - gl), &r_d, 2);
+          __builtin_memcpy(pe + 16u * (l0 + ll) + 2u * (rh - gl), &r_e, 2);
+        }
+      }
+    }
+    wave_sync();
+    __builtin_memcpy(&cw, pc + 8u * lane, 8); __builtin_memcpy(&qw, pq + 8u * lane, 8);
+    __builtin_memcpy(&dv, pd + 16u * lane, 16); __builtin_memcpy(&ev, pe + 16u * lane, 16);
+  }
   // ---- cD / cM / cE (vanilla_caller.rs:1800-1810): max / min depth, sum of errors / sum of depths as f32, per half -------------------------
   uint32_t maxd, mind, sumd = 0, sume = 0;
   {
@@ -540,6 +584,9 @@ __global__ __launch_bounds__(256, FGX_EMIT_OCC) void k_emit(EmitParams P) {
   // loads, the valid flags and then each record's fields were dependent memory round trips of their own
   __shared__ __align__(16) EndDesc sD[4][3];
   static_assert(sizeof(EndDesc) == 96, "EndDesc is copied as six 16-byte pieces");
+#if FGX_EMIT_PAIR
+  __shared__ __align__(16) uint8_t sPatch[4][EMIT_PATCH_BYTES];   // emit_pair: where k_call_full's answers meet the family's columns
+#endif
   uint32_t fam = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
   const uint32_t lane = threadIdx.x & 63, wv = (threadIdx.x >> 6) & 3;
   if (P.fam_list) {   // the merge of a direct-records batch: only the families that left the split pipeline have descriptors
@@ -562,6 +609,9 @@ __global__ __launch_bounds__(256, FGX_EMIT_OCC) void k_emit(EmitParams P) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const u32x4 piece = ((const u32x4*)&P.ends[s0])[lane < 6 * ns ? lane : 0u];
   const uint64_t oo = P.out_off[s0 + (lane < ns ? lane : 0u)];   // (both loads leave before either is waited for)
+#if FGX_EMIT_PAIR
+  const uint32_t fr_flag = (P.full_flag && !P.fam_list) ? (uint32_t)P.full_flag[fam] : 0u;   // ... and this one: does the pair writer apply k_call_full's answers for the family?
+#endif
   if (lane < 6 * ns) ((u32x4*)&sD[wv][0])[lane] = piece;
   wave_sync();
   const bool v0 = uni(sD[wv][0].valid) != 0, v1 = ns > 1 && uni(sD[wv][1].valid) != 0, v2 = ns > 2 && uni(sD[wv][2].valid) != 0;
@@ -572,7 +622,12 @@ __global__ __launch_bounds__(256, FGX_EMIT_OCC) void k_emit(EmitParams P) {
   };
   if (v0) { EmitLoads R0; emit_load(P, sD[wv][0], off_of(0), lane, R0); emit_store(P, sD[wv][0], lane, R0); }   // a fragment record: families of single reads
 #if FGX_EMIT_PAIR
-  if (!v0 && v1 && v2 && emit_pair(P, &sD[wv][0], off_of(1), off_of(2), lane)) return;   // (round 6) the usual pair family: both records side by side in the halves of the wavefront
+  {
+    // the family's range of results: the word the packed build left in the fragment slot's descriptor (fastpath.h: full_range_word)
+    const uint64_t fr_word = uniform_u64(sD[wv][0].col_off);
+    const uint32_t fr_cnt = uni(fr_flag) ? (uint32_t)(fr_word >> 32) & 0xFFFFu : 0u;
+    if (!v0 && v1 && v2 && emit_pair(P, &sD[wv][0], off_of(1), off_of(2), lane, &sPatch[wv][0], (uint32_t)fr_word, fr_cnt <= FULL_RESULT_MAX_ITEMS ? fr_cnt : 0u)) return;
+  }   // (round 6) the usual pair family: both records side by side in the halves of the wavefront
 #endif
   // the two records of a pair family: both records' loads, then both records' stores
   EmitLoads R1, R2;

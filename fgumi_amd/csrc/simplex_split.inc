@@ -1440,8 +1440,9 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
         if (need) {
           uint8_t* const it = W + ibase + s2_mul24(icnt + per_cold * (uint32_t)__popcll(needm & below0), (uint32_t)sizeof(FullItem));
           if (on) *(uint16_t*)(it + (j >> 4) * (uint32_t)sizeof(FullItem) + 8 + 2 * (j & 15u)) = (uint16_t)ob16;   // observation j of the column: item j / 16
-          if (j == 0u) { *(uint64_t*)it = col_base + oc_l; *(uint32_t*)(it + 40) = 0; *(uint32_t*)(it + 44) = FULL_ITEM_OBS | m; }
-          if (j == 16u && per_cold > 1u) { *(uint32_t*)(it + sizeof(FullItem) + 40) = 0; *(uint32_t*)(it + sizeof(FullItem) + 44) = FULL_ITEM_CONT; }
+          // (the `obs` word of these items is free: the family's index + 1, through which k_call_full finds out whether the pair writer applies the answer — fastpath.h, FullResult)
+          if (j == 0u) { *(uint64_t*)it = col_base + oc_l; *(uint32_t*)(it + 40) = g + 1u; *(uint32_t*)(it + 44) = FULL_ITEM_OBS | m; }
+          if (j == 16u && per_cold > 1u) { *(uint32_t*)(it + sizeof(FullItem) + 40) = g + 1u; *(uint32_t*)(it + sizeof(FullItem) + 44) = FULL_ITEM_CONT; }
         } else if (col_on && j == r1) {
           const uint32_t nobs = one ? 1u : 2u;
           uint32_t ob, oq;
@@ -1532,6 +1533,8 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     if (lane == 0) ((uint32_t*)&KA::of(P).split_out[g])[7] = (mx & 0xFFu) | ((mn & 0xFFu) << 8) | (((mx >> 16) & 0xFFu) << 16) | (((mn >> 16) & 0xFFu) << 24);   // cD / cM of both records
     dir_tables(type_a == 0u ? RA.size : 0u, type_a == 0u ? 0u : RA.size, RB.size);
   }
+  uint32_t fr_first = 0;                // where the family's items lie, for the pair writer (fastpath.h, FullResult): first slot of the pool, in one piece
+  bool fr_whole = true;
   if (icnt) {   // the family's items: LDS -> the reserved range, 16 bytes per lane and step; a range that crosses the end of its list
                 // continues in the next list (one more, synchronous, reservation — rare)
     wave_sync();
@@ -1544,10 +1547,11 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
       // a column of several consecutive items must not be cut at the end of a list: the reservation that does not hold the WHOLE family is
       // filled with continuation items (k_call_full skips them) and the family's items go to the next list that holds them all
       for (;;) {
-        if (base < full_cap && icnt <= full_cap - base) {
+        if (full_range_whole(base, icnt, full_cap)) {
           const uint4* src = (const uint4*)(W + ibase);
           uint4* dst = (uint4*)(full_items + ((size_t)l * full_cap + base));
           for (uint32_t c = lane; c < 3 * icnt; c += 64) dst[c] = src[c];
+          fr_first = l * full_cap + base;
           break;
         }
         if (base < full_cap) {
@@ -1560,7 +1564,9 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
         if (lane == 0) b2 = atomicAdd(&KA::of(P).full_count[l], icnt);
         base = uni(b2);
       }
-    } else
+    } else {
+    fr_whole = full_range_whole(base, icnt, full_cap);          // (a range that crosses the end of its list is cut: k_call_full scatters that family's answers)
+    fr_first = l * full_cap + base;
     for (;;) {
       const uint32_t rem = icnt - done;
       const uint32_t fit = base < full_cap ? (rem < full_cap - base ? rem : full_cap - base) : 0u;
@@ -1575,6 +1581,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
       if (lane == 0) b2 = atomicAdd(&KA::of(P).full_count[l], icnt - done);
       base = uni(b2);
     }
+    }
     if (overflow) {   // every list is full: the general path redoes the family (its result is withdrawn: no records, nothing counted)
       leave(3u, 0, 0, 0, 0, 0, 0);
       if (DIRECT) dir_tables(0, 0, 0);                         // (its records are in place already: the host takes the batch through the merge)
@@ -1582,6 +1589,9 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
       return;
     }
   }
+  // (packed build, scratch path) the range, in the 64-bit word `col_off` of the family's fragment EndDesc — k_split_finish touches only `valid` there
+  if constexpr (COLS == 1 && DIRECT == 0) { if (lane == 0) KA::of(P).ends[slot0].col_off = full_range_word(fr_first, icnt, fr_whole); }
+  (void)fr_first; (void)fr_whole;
   PH(8)
 }
 
@@ -1644,6 +1654,7 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
   const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63;
   uint32_t c_total = 0, c_cons = 0, c_insuf = 0, c_zero = 0, c_orphan = 0, c_agree = 0, c_dis = 0, c_corr = 0, c_packed = 0, c_classic = 0, c_clean = 0;
+  uint32_t c_apply = 0, c_cut = 0, c_over = 0;               // (fgx_debug_last_full_results: families whose answers the pair writer applies / refused because their items are not in one piece)
   if (gi < count) {
     const uint32_t g = P.group_list ? P.group_list[gi] : P.g0 + gi;
     const SplitOut O = P.split_out[g];
@@ -1740,6 +1751,11 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
           rec_off += size;
         }
       }
+      // (round 7) does the pair writer apply k_call_full's answers for this family (fastpath.h, FullResult)?  The range of its items: the word
+      // the packed build left in the fragment slot's descriptor; the pair: emit_pair's own condition on the fields written below.
+      const bool fr_pair = P.full_results && !direct && padded && O.ne == 2 && O.type_a == 1;
+      const uint64_t fr_word = fr_pair ? P.ends[slot0].col_off : 0ull;
+      uint32_t fr_cbl[2] = {0u, 0u}, fr_rxl[2] = {0u, 0u}, fr_size0 = 0u;
       for (uint32_t k = 0; k < (direct ? 0u : (uint32_t)O.ne); k++) {
         const uint32_t Lc = k == 0 ? O.lc_a : O.lc_b, e_type = k == 0 ? O.type_a : 2u;
         const uint32_t fk = k == 0 ? O.fk_a : O.fk_b, kept = k == 0 ? O.kept_a : O.kept_b;
@@ -1781,6 +1797,18 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
         u32x4* dst = (u32x4*)&P.ends[slot0 + e_type];
         dst[0] = p0; dst[1] = p1; dst[2] = p2; dst[3] = p3; dst[4] = p4; dst[5] = p5;
         P.rec_sizes[slot0 + e_type] = (uint64_t)size + 4;
+        fr_cbl[k & 1u] = hcb ? cbl : 0u; fr_rxl[k & 1u] = rx_cnt ? rx_ulen : 0u;
+        if (k == 0) fr_size0 = size;
+      }
+      if (fr_pair) {
+        // (both descriptors carry the family's first record and its MI value; R2's columns lie s2_padded_b - S2_PAD_FRONT behind R1's, and
+        // its record follows R1's in the scan of the sizes)
+        const uint32_t items = (uint32_t)(fr_word >> 32) & 0xFFFFu;
+        const bool whole = ((fr_word >> 48) & 1u) != 0;
+        const bool taken = emit_pair_takes(O.lc_a, O.lc_b, P.prefix_len + 1u + R0.mi_len, P.rg_len, R0.mi_len, fr_cbl[0], fr_cbl[1], fr_rxl[0], fr_rxl[1], true,
+                                           (uint64_t)(s2_padded_b(O.lc_a) - S2_PAD_FRONT), (uint64_t)fr_size0 + 4ull);
+        if (full_results_family(true, true, whole, items, taken)) { c_apply = 1u; P.full_flag[g] = 1; }
+        else if (taken) { if (!whole) c_cut = 1u; else c_over = 1u; }   // (its answers are scattered: a range cut at a list's end / more items than the writer loads)
       }
     }
   }
@@ -1806,5 +1834,14 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
     if (t_classic) atomicAdd(&st[29], (unsigned long long)t_classic);
     if (t_clean) atomicAdd(&st[30], (unsigned long long)t_clean);
     if (t_packed - t_clean) atomicAdd(&st[31], (unsigned long long)(t_packed - t_clean));
+  }
+  if (P.full_results) {
+    const uint32_t t_apply = wave_sum(c_apply), t_cut = wave_sum(c_cut), t_over = wave_sum(c_over);
+    if (lane == 0) {
+      unsigned long long* fs = P.full_stats + (size_t)((blockIdx.x * 4 + (threadIdx.x >> 6)) & (STAT_SLOTS - 1)) * FULL_STATS_STRIDE;
+      if (t_apply) atomicAdd(&fs[2], (unsigned long long)t_apply);
+      if (t_cut) atomicAdd(&fs[3], (unsigned long long)t_cut);
+      if (t_over) atomicAdd(&fs[4], (unsigned long long)t_over);
+    }
   }
 }
