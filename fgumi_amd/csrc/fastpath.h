@@ -40,9 +40,9 @@ struct DuplexDesc {         // one duplex consensus record (slot 3g+1 = R1, 3g+2
   uint8_t mi_len, cb_len, rx_len, type;
   uint8_t has_cb, has_rx, valid, has_ba;
   char rx[FAST_RX_CAP];
-  uint8_t meth;             // methylation-aware mode (k_family_wave<1, 1>; in what was padding): bit 0 the AB-side strand's call was annotated, bit 1 the BA-side
+  uint8_t meth;             // methylation-aware mode (k_family_wave<1, 1> and <1, 1, 1>; in what was padding): bit 0 the AB-side strand's call was annotated, bit 1 the BA-side
                             // strand's, bit 2 a lone strand passed through is the BA one (is_ba_only: its tags are bm / bu / bt and its MM strand is G-m)
-  uint8_t capped;           // --max-reads-per-strand bit a read set of the molecule (k_family_wave<1, 0, 1>; padding too): the duplex error recount (cE / ce) reads the
+  uint8_t capped;           // --max-reads-per-strand bit a read set of the molecule (k_family_wave<1, 0, 1> and <1, 1, 1>; padding too): the duplex error recount (cE / ce) reads the
                             // counts over ALL source reads from col_obs_all, col_obs holds the counts of the scoring reads (depths)
 };
 static_assert(sizeof(DuplexDesc) == 96, "DuplexDesc: the methylation byte and the cap flag lie in the padding");

@@ -35,7 +35,7 @@
 // the general path raises the reference's fatal error), unmapped reads of the duplex / CODEC callers and of the methylation-aware mode, an unmapped
 // record that carries CIGAR ops, more than FAST_MAX_READS reads or more LDS than the launch provides,
 // duplex / CODEC molecules with indels.  A per-strand read cap that bites is decided here (the CAP builds of k_family_wave<1> / <2> and of the
-// duplex record writers); deferred under one: a duplex cap of 0 and the methylation-aware duplex build.  The simplex kernels take unmapped records
+// duplex record writers, k_family_wave<1, 1, 1> in the methylation-aware mode); deferred under one: a duplex cap of 0.  The simplex kernels take unmapped records
 // (`fgumi group --allow-unmapped`): a read without a CIGAR, no mate clip, no overlap step; ends that are uniform by flag stay where a mapped family of their
 // shape runs, an end with mapped AND unmapped reads is k_family_wave<0>'s (drop_unmapped_if_any_mapped) — up to 64 records and without indel reads, else
 // deferred.  See DESIGN.md 3.
@@ -1134,8 +1134,10 @@ inline void build_fw_image(FwLds& L, const ConsensusTables& t) {
 
 // METH 1 (duplex only): the methylation-aware mode — per read set the anchor read's place on the reference, the unconverted / converted counts of every
 // column and converted bases read as unconverted ones before they are observed (see 6D); molecules with a record of more than one CIGAR op are deferred.
-// CAP 1 (duplex, METH 0): the build of a caller with --max-reads-per-strand — a read set above the cap is scored over its `cap` lowest name ranks, walked in
+// CAP 1 (duplex): the build of a caller with --max-reads-per-strand — a read set above the cap is scored over its `cap` lowest name ranks, walked in
 // (rank, file order), and the observations of ALL its reads are counted beside them for the duplex error recount (see 5D / 6D); CAP 0 is the kernel without any of it.
+// METH 1 with CAP 1: the reference annotates and normalises a set AHEAD of the cap, so a capped set's anchor, its unconverted / converted counts and the recount's
+// bases are those of every read (count_all), normalised; the scoring loops normalise what they observe and leave the counts alone.
 // CAP 1 (CODEC): the build of a caller with --max-reads-per-strand — the R1 list and the R2 list are cut to their `cap` lowest name ranks ahead of the geometry (5C).
 // Wave-aggregated append of the columns (and UMI characters) whose call needs call_full to the global FullItem lists (k_call_full works through them
 // densely): one atomic with its return value per wavefront and list tried; a full list chains to the next one, only a globally full pool overflows.  Every
@@ -1909,7 +1911,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       elen[k] = sm[k] ? wave_max(((sm[k] >> lane) & 1) ? final_len : 0) : 0;
       eoff[k] = tot; tot += elen[k];
     }
-    // without the CAP build (the methylation-aware mode), and with a cap of 0 (no set has a consensus): the general path
+    // without the CAP build, and with a cap of 0 (no set has a consensus): the general path
     if (cap_bites && (CAP == 0 || P.dmax_reads == 0)) { to_defer(); return; }
   }
   const uint32_t plen1 = (em[0] && em[3]) ? (elen[0] < elen[3] ? elen[0] : elen[3]) : 0;    // R1 duplex: AB-R1 with BA-R2
@@ -1930,11 +1932,17 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   // A capped set's columns once more, counting only: the observations of EVERY read of the set (the scoring ones included) under the masking rule of the
   // column loops — what the duplex error recount of the record writers works from (duplex_consensus counts over source_reads, which the cap does not touch).
   // The same number of passes in every lane: the cross-lane reads stay in wave-uniform control flow.
-  auto count_all = [&](unsigned long long all, uint32_t len_k, uint32_t off_k) {     // (by value: no dynamically indexed local array)
+  // The methylation-aware mode (METH with CAP) annotates here: annotate_and_normalize runs over the WHOLE set ahead of the cap, so the unconverted / converted
+  // counts of a capped set's columns are these reads', and what is counted for the recount is the NORMALISED base (source_reads stays the normalised set);
+  // `is_c_of`: the set's ref_is_c, `tc` / `vc`: its unconverted / converted code in consensus orientation.
+  auto count_all = [&](unsigned long long all, uint32_t len_k, uint32_t off_k, auto&& is_c_of, uint32_t tc, uint32_t vc) {     // (by value: no dynamically indexed local array)
     for (uint32_t p0 = 0; p0 < len_k; p0 += 64) {
       const uint32_t p = p0 + lane;
       const bool incol = p < len_k;
       uint32_t cnt = 0;
+      bool is_c = false;
+      uint32_t mu = 0, mt = 0;
+      if constexpr (METH != 0) is_c = incol && is_c_of(p);
       for (unsigned long long m = all; m; m &= m - 1) {
         const uint32_t r = (uint32_t)__builtin_ctzll(m);
         const uint32_t x0 = rlane(d0, r), x1 = rlane(d1, r), x2 = rlane(d2, r);
@@ -1944,11 +1952,13 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
         const uint32_t bb = W[(x0 & 0xFFFF) + (idx >> 1)];
         const uint32_t c = (bb >> ((~idx & 1) << 2)) & 15;
         const uint32_t q = W[(x0 >> 16) + idx];
-        const uint32_t co = rv ? __builtin_bitreverse32(c) >> 28 : c;
+        uint32_t co = rv ? __builtin_bitreverse32(c) >> 28 : c;
         const bool masked = p < (x2 & 0xFFFF) && q < min_bq;
+        if constexpr (METH != 0) { if (is_c && valid && !masked) { if (co == tc) mu++; else if (co == vc) { mt++; co = tc; } } }
         if (valid && !masked && __popc(co) == 1) cnt += 1u << (8 * (uint32_t)__builtin_ctz(co));
       }
       if (incol) P.col_obs_all[col_base + off_k + p] = cnt;
+      if constexpr (METH != 0) { if (incol) { const uint64_t o = col_base + off_k + p; P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; } }
     }
   };
 #pragma unroll
@@ -1959,7 +1969,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     const uint32_t plen = (k == 0 || k == 3) ? plen1 : plen2;
     const bool by_rank = CAP != 0 && capped[k];                    // a capped set's reads enter a column in (rank, file order): cap_ord
     // Methylation-aware mode (annotate_and_normalize, vanilla_caller.rs:781-860; methylation.rs:193-242): the call's anchor is the LAST longest
-    // source read of the set (max_by_key; file order = lane order), taken over all its reads — a cap that bites is deferred above.  Every read here
+    // source read of the set (max_by_key; file order = lane order), taken over ALL its reads: em[k], not the scoring reads a cap leaves — the anchor of a
+    // capped set may be a read the cap drops, and longer than the consensus (the annotation is truncated to it: the columns end at elen[k]).  Every read here
     // is one aligned block, alone or between clips — to the reference ONE M op of T bases, T = the lengths of all its ops, hard clips included —, so column
     // p lies at the anchor's pos + p (forward) or at pos + T - 1 - p (reverse: the columns run in read orientation; with trailing clips that is NOT the
     // last aligned base).  The strand of the call is is_top_strand of the anchor's flags (methylation.rs:392-398): C / T against a reference C, else G / A
@@ -1975,7 +1986,8 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
     uint32_t a_nruns = 0;
     uint32_t tcode = 0, vcode = 0, target = 0;                     // unconverted / converted read base as 4-bit codes in consensus orientation; the reference base
     if constexpr (METH != 0) {
-      const unsigned long long lm = members & __ballot(final_len == elen[k]);
+      unsigned long long lm = members & __ballot(final_len == elen[k]);
+      if constexpr (CAP != 0) { if (by_rank) { const uint32_t alen = wave_max(((em[k] >> lane) & 1) ? final_len : 0); lm = em[k] & __ballot(final_len == alen); } }
       const uint32_t an = 63u - (uint32_t)__clzll((long long)lm);
       const uint32_t a_flags = rlane(flags, an), a_tot = rlane(tot_len, an);   // (T: l_seq of a read of one op; more with hard clips)
       const int32_t a_pos = (int32_t)rlane((uint32_t)pos, an), a_ref = (int32_t)rlane((uint32_t)ref_id, an);
@@ -2094,12 +2106,12 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
           }
           P.col_obs[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24);
           if constexpr (CAP != 0) { if (any_capped && !by_rank) P.col_obs_all[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24); }
-          if constexpr (METH != 0) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; }
+          if constexpr (METH != 0) { if (!by_rank) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; } }   // (a capped set: count_all's, over every read)
           dm_fu[k] = depth > dm_fu[k] ? depth : dm_fu[k];
           if (p < plen) dm_tr[k] = depth > dm_tr[k] ? depth : dm_tr[k];
         }
       }
-      if constexpr (CAP != 0) { if (by_rank) count_all(em[k], elen[k], eoff[k]); }
+      if constexpr (CAP != 0) { if (by_rank) count_all(em[k], elen[k], eoff[k], ref_is_c, tcode, vcode); }
       continue;
     }
     // (a single-read set: the read's fields once, by every lane, ahead of the column loop — its trip count differs from lane to lane)
@@ -2164,11 +2176,11 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
       }
       P.col_obs[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24);
       if constexpr (CAP != 0) { if (any_capped && !by_rank) P.col_obs_all[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24); }
-      if constexpr (METH != 0) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; }
+      if constexpr (METH != 0) { if (!by_rank) { P.meth_flag[o] = is_c ? 1 : 0; P.meth_u[o] = (uint16_t)mu; P.meth_t[o] = (uint16_t)mt; } }
       dm_fu[k] = depth > dm_fu[k] ? depth : dm_fu[k];
       if (p < plen) dm_tr[k] = depth > dm_tr[k] ? depth : dm_tr[k];
     }
-    if constexpr (CAP != 0) { if (by_rank) count_all(em[k], elen[k], eoff[k]); }
+    if constexpr (CAP != 0) { if (by_rank) count_all(em[k], elen[k], eoff[k], ref_is_c, tcode, vcode); }
   }
   if (__any(odd_base)) { to_defer(); return; }
 #pragma unroll
@@ -3054,7 +3066,7 @@ struct Batch {
   // The duplex caller in the mode: the wavefront kernel's <1, 1> build annotates and normalises the four read sets of a molecule in its column
   // loops, the record writers' <1> builds apply the conversion-artifact rule, am/au/at, bm/bu/bt, MM/ML/cu/ct follow RX (duplex_meth.inc).
   const bool meth_dup = duplex && meth_on;
-  const bool dup_cap = duplex && !meth_on && o.duplex_max_reads_per_strand > 0;   // the CAP builds of k_family_wave<1> and of the duplex record writers
+  const bool dup_cap = duplex && o.duplex_max_reads_per_strand > 0;   // the CAP builds of k_family_wave<1> and of the duplex record writers
   // Simplex without --trim: which head of the launch chain?  Shallow families (the mean family fits a quarter of a wave's LDS
   // slice) start at k_simplex_seg<4>; everything else at the split pipeline (k_split_parse + k_split_cols, simplex_split.inc),
   // whose record kernel also leaves what k_col_bound would (column bound, byte-span descriptor).
@@ -3283,6 +3295,7 @@ struct Batch {
       FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<2>);
       FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1, 1>);
       FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1, 0, 1>);
+      FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<1, 1, 1>);
       FGX_LDS_ATTR(WAVES_PER_BLOCK * 22016, k_family_wave<2, 0, 1>);
       fp.lds_attr_set = true;
     }
@@ -3524,6 +3537,7 @@ struct Batch {
       const size_t lds = (size_t)S.wpb * S.bytes;
       if (codec && o.codec_max_reads_per_strand > 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<2, 0, 1>), grid, block, lds, s, PS, n_cur);
       else if (codec) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<2>), grid, block, lds, s, PS, n_cur);
+      else if (meth_dup && dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1, 1, 1>), grid, block, lds, s, PS, n_cur);
       else if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1, 1>), grid, block, lds, s, PS, n_cur);
       else if (dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1, 0, 1>), grid, block, lds, s, PS, n_cur);
       else if (duplex) FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<1>), grid, block, lds, s, PS, n_cur);
@@ -3797,7 +3811,8 @@ struct Batch {
       DE.meth_flag = P.meth_flag;
       DE.col_obs_all = P.col_obs_all;
       FGX_LAUNCH(HIP_KERNEL_NAME(k_count_slow<DuplexDesc>), per_slot, dim3(256), 0, s, DE.ends, 0u, n_slots, DE.prefix_len, DE.rg_len, DE.n_slow);
-      if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<1>), wave_per_slot, dim3(256), 0, s, DE);
+      if (meth_dup && dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<1, 1>), wave_per_slot, dim3(256), 0, s, DE);
+      else if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<1>), wave_per_slot, dim3(256), 0, s, DE);
       else if (dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<0, 1>), wave_per_slot, dim3(256), 0, s, DE);
       else FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex_fast<0>), wave_per_slot, dim3(256), 0, s, DE);
     } else if (!direct || !dir_pure) {
@@ -3830,6 +3845,7 @@ struct Batch {
     read_counters();
     if ((duplex || codec) && (uint32_t)h_misc[MISC_N_SLOW] != 0) {     // records the fast writer left: the per-field kernel, then the counters again (the CODEC writer counts bases)
       if (codec) FGX_LAUNCH(k_emit_codec, wave_per_slot, dim3(256), 0, s, CE);
+      else if (meth_dup && dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<1, 1>), wave_per_slot, dim3(256), 0, s, DE);
       else if (meth_dup) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<1>), wave_per_slot, dim3(256), 0, s, DE);
       else if (dup_cap) FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<0, 1>), wave_per_slot, dim3(256), 0, s, DE);
       else FGX_LAUNCH(HIP_KERNEL_NAME(k_emit_duplex<0>), wave_per_slot, dim3(256), 0, s, DE);

@@ -15,6 +15,9 @@
   --indel-fraction F (both callers; instead of --clip-fraction): that share of the reads carries a deletion (`aMdDbM`, d 1 .. 3 bases; the mate's MC follows).
       In the mode such a family / molecule is deferred by the first device pass; with FGX_METH_CANON=1 in the environment the canonical second pass decides it on the
       device.  The line carries `canonicalised_molecules` (fgx_debug_last_deferral) beside `deferred_families`.
+  --max-reads-per-strand N (duplex): the caller's per-strand read cap in every leg — k_family_wave<1, 1, 1> in the mode, <1, 0, 1> with the mode off; the
+      line carries the cap.  With 6 + 6 pairs per molecule a cap below 6 bites every molecule.  Together with --host-entry-only (FGX_LIB on a library whose
+      device pipeline defers such molecules): what its users got, the device pass and the deferred subset on the general path.
   --batch-cache DIR: a comparison of two libraries (FGX_LIB) alternates PROCESSES over one batch; simulating and clipping 16 M reads on the host takes
       minutes per process and the measurement a second, so the batch and the genome are kept as .npy files in DIR (the caller's to delete) between them.
 
@@ -155,6 +158,7 @@ def main():
     ap.add_argument("--clip-fraction", type=float, default=0.0, help="share of the reads that carries soft clips at both ends")
     ap.add_argument("--indel-fraction", type=float, default=0.0, help="share of the reads that carries a deletion (not together with --clip-fraction)")
     ap.add_argument("--repeats", type=int, default=1, help="runs of the em_seq / mode_off legs, alternating (the line then holds lists)")
+    ap.add_argument("--max-reads-per-strand", type=int, default=None, help="duplex: --max-reads-per-strand of the caller, in every leg")
     ap.add_argument("--batch-cache", default=None, help="directory that keeps the simulated (and clipped) batch and the genome between runs of the same shape")
     ap.add_argument("--host-entry-only", action="store_true", help="only the host-entry leg over the first --host-sample families (device pass + deferred subset)")
     a = ap.parse_args()
@@ -168,6 +172,7 @@ def main():
     sim = dict(family_size=depth, duplex=1) if duplex else dict(family_size=depth)
     from fgumi_amd import GroupedReads
     assert not (a.clip_fraction > 0 and a.indel_fraction > 0), "--clip-fraction or --indel-fraction"
+    assert a.max_reads_per_strand is None or duplex, "--max-reads-per-strand is the duplex caller's"
     key = os.path.join(a.batch_cache, f"{a.caller}_{a.families}_{depth}_{a.clip_fraction}" + (f"_indel{a.indel_fraction}" if a.indel_fraction > 0 else "")) if a.batch_cache else None
     lib.fgx_debug_last_deferral.restype = None
     lib.fgx_debug_last_deferral.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
@@ -204,10 +209,13 @@ def main():
     line = {"workload": f"{what}, device-resident, EM-Seq mode, {len(genome) >> 20} MiB genome in HBM", "caller": a.caller, "raw_reads": n_reads,
             "clip_fraction": a.clip_fraction, "clipped_reads": n_clipped if a.indel_fraction == 0 else 0, "indel_fraction": a.indel_fraction,
             "indel_reads": n_clipped if a.indel_fraction > 0 else 0, "FGX_METH_CANON": os.environ.get("FGX_METH_CANON")}
+    if a.max_reads_per_strand is not None:
+        line["max_reads_per_strand"] = a.max_reads_per_strand
 
     def make(mode):
         if duplex:
-            return DuplexConsensusCaller("", "A", [1, 1, 1], cell_tag="CB", overlapping_consensus=True, methylation_mode=int(mode) if mode is not None else 0)
+            return DuplexConsensusCaller("", "A", [1, 1, 1], cell_tag="CB", overlapping_consensus=True, methylation_mode=int(mode) if mode is not None else 0,
+                                         max_reads_per_strand=a.max_reads_per_strand)
         kw = dict(min_reads=1, min_consensus_base_quality=2, cell_tag="CB")
         if mode is not None:
             kw["methylation_mode"] = mode
