@@ -70,7 +70,12 @@ int fgx_bgzf_inflate(const uint8_t* raw, uint64_t raw_len, uint32_t threads, uin
   std::atomic<int> bad(0);
   run_pool(pick_threads(threads, blocks.size()), blocks.size(), [&](size_t i) {
     const Block& b = blocks[i];
-    if (b.isize == 0) return;
+    if (b.isize == 0) {                        // (an empty block: nothing to inflate, but its CRC-32 field must be that of nothing — as the device's k_bgzf_crc checks it)
+      uint32_t crc0;
+      memcpy(&crc0, raw + b.in_off + b.in_size - 8, 4);
+      if (crc0 != 0) bad = 1;
+      return;
+    }
     const uint32_t xlen = raw[b.in_off + 10] | (raw[b.in_off + 11] << 8);
     z_stream zs;
     memset(&zs, 0, sizeof(zs));

@@ -67,8 +67,11 @@ int fgx_bgzf_recompress_file(const char* in_path, const char* out_path, uint32_t
 const char* fgx_pipeline_last_error(void) { return t_perr.c_str(); }
 
 // The device's BGZF inflate (+ CRC-32 check) alone, for measurements and tests: the whole blocks of raw[0 .. raw_len) are uploaded once and
-// inflated `reps` times; *ms = average device time of one pass (HIP events), *inflated_len = bytes produced.  When `out` is given
-// (inflated_cap bytes) the stream of the last pass is copied there.  Returns 0, or non-zero with fgx_last_error(c).
+// inflated — a warm-up pass, then `reps` timed passes; *ms = average device time of one timed pass (HIP events), *inflated_len = bytes
+// produced.  When `out` is given (inflated_cap bytes) the stream of the last pass is copied there.  The output buffer is filled with
+// INFL_POISON before the first pass, and reps == 0 runs that first pass ONLY (*ms = 0): what comes back is then what ONE pass over poisoned
+// memory produced — with a second pass into the same buffer, a match the resolve pass skipped, or copied from a byte that was not final
+// yet, is repaired by the bytes the pass before left there (tests/test_gpu_bgzf_device.py).  Returns 0, or non-zero with fgx_last_error(c).
 int fgx_bgzf_inflate_device_bench(fgx_caller* c, const uint8_t* raw, uint64_t raw_len, uint32_t reps, double* ms, uint64_t* inflated_len, uint8_t* out,
                                   uint64_t inflated_cap) {
   if (!c || !raw || !ms || !inflated_len) return 1;
@@ -117,21 +120,54 @@ int fgx_bgzf_inflate_device_bench(fgx_caller* c, const uint8_t* raw, uint64_t ra
     fgx::hip_check(hipEventCreate(&R.e0), "event"); fgx::hip_check(hipEventCreate(&R.e1), "event");
     const hipEvent_t e0 = R.e0, e1 = R.e1;
     int rc = 0;
-    fgx::bgzf_inflate_launch(s, d_raw.as<uint8_t>(), d_blk.as<fgx::BgzfDevBlock>(), (uint32_t)dev.size(), d_out.as<uint8_t>(), d_status, h_status, ent_bytes ? R.d_ent.p : nullptr, ent_bytes);   // warm-up
+    // poison first (drained before the first kernel is queued: hipMemsetAsync is not trusted to keep its place among kernels, boundaries.hip)
+    constexpr int INFL_POISON = 0xA5;
+    fgx::hip_check(hipMemsetAsync(d_out.p, INFL_POISON, infl + 256, s), "memset");
+    fgx::hip_check(hipStreamSynchronize(s), "sync");
+    fgx::bgzf_inflate_launch(s, d_raw.as<uint8_t>(), d_blk.as<fgx::BgzfDevBlock>(), (uint32_t)dev.size(), d_out.as<uint8_t>(), d_status, h_status, ent_bytes ? R.d_ent.p : nullptr, ent_bytes);   // warm-up (reps == 0: the only pass)
     fgx::hip_check(hipStreamSynchronize(s), "sync");
     if (fgx::bgzf_inflate_status(c, *h_status) != 0) rc = 1;
     fgx::hip_check(hipEventRecord(e0, s), "event");
-    for (uint32_t r = 0; r < (reps ? reps : 1u) && rc == 0; r++)
+    for (uint32_t r = 0; r < reps && rc == 0; r++)
       fgx::bgzf_inflate_launch(s, d_raw.as<uint8_t>(), d_blk.as<fgx::BgzfDevBlock>(), (uint32_t)dev.size(), d_out.as<uint8_t>(), d_status, h_status, ent_bytes ? R.d_ent.p : nullptr, ent_bytes);
     fgx::hip_check(hipEventRecord(e1, s), "event");
     fgx::hip_check(hipStreamSynchronize(s), "sync");
-    if (rc == 0 && fgx::bgzf_inflate_status(c, *h_status) != 0) rc = 1;
+    if (rc == 0 && reps && fgx::bgzf_inflate_status(c, *h_status) != 0) rc = 1;
     float t = 0;
     fgx::hip_check(hipEventElapsedTime(&t, e0, e1), "elapsed");
-    *ms = (double)t / (double)(reps ? reps : 1u);
+    *ms = reps ? (double)t / (double)reps : 0.0;
     *inflated_len = infl;
     if (rc == 0 && out && inflated_cap >= infl && infl) fgx::hip_check(hipMemcpy(out, d_out.p, infl, hipMemcpyDeviceToHost), "D2H");
     return rc;
+  } catch (const std::exception& ex) { c->err = ex.what(); return 3; }
+}
+
+// The device's BGZF deflate alone, for tests: in[0 .. len) goes to the device (64 zeroed bytes of slack behind it), bgzf_deflate_device makes its
+// BGZF blocks (0xff00 bytes each, no EOF marker), and the packed blocks come back in out[0 .. *out_len).  Returns 0, or non-zero with
+// fgx_last_error(c) (`cap` too small included; *out_len then says what was needed).
+int fgx_bgzf_deflate_device_bench(fgx_caller* c, const uint8_t* in, uint64_t len, uint8_t* out, uint64_t cap, uint64_t* out_len) {
+  if (!c || (!in && len) || !out_len) return 1;
+  c->err.clear();
+  *out_len = 0;
+  if (len == 0) return 0;
+  try {
+    fgx::hip_check(hipSetDevice(c->device), "hipSetDevice");
+    // everything this entry allocates is released on every way out (a hip_check that throws included)
+    struct Scope {
+      fgx::DevBuf d_in, d_slots, d_scratch, d_meta, d_packed;
+      ~Scope() { d_in.free_(); d_slots.free_(); d_scratch.free_(); d_meta.free_(); d_packed.free_(); }
+    } R;
+    hipStream_t s = c->stream;
+    R.d_in.reserve(len + 64);
+    fgx::hip_check(hipMemcpyAsync(R.d_in.p, in, len, hipMemcpyHostToDevice, s), "H2D");
+    fgx::hip_check(hipMemsetAsync((uint8_t*)R.d_in.p + len, 0, 64, s), "memset");
+    fgx::hip_check(hipStreamSynchronize(s), "sync");
+    uint64_t plen = 0;
+    if (fgx::bgzf_deflate_device(c, R.d_in.as<uint8_t>(), len, R.d_slots, R.d_scratch, R.d_meta, R.d_packed, &plen) != 0) return 1;
+    *out_len = plen;
+    if (!out || cap < plen) { c->err = "fgx_bgzf_deflate_device_bench: the output buffer holds " + std::to_string(cap) + " bytes, the blocks take " + std::to_string(plen); return 2; }
+    if (plen) fgx::hip_check(hipMemcpy(out, R.d_packed.p, plen, hipMemcpyDeviceToHost), "D2H");
+    return 0;
   } catch (const std::exception& ex) { c->err = ex.what(); return 3; }
 }
 

@@ -371,8 +371,13 @@ struct PipelineT {
           std::atomic<int> bad(0);
           pool.parallel_for(c.blocks.size(), 8, [&](size_t i, unsigned w) {
             const Block& b = c.blocks[i];
-            if (b.isize == 0) return;
             const uint8_t* raw = c.raw;
+            if (b.isize == 0) {                                   // (an empty block: nothing to inflate, but its CRC-32 field must be that of nothing — as k_bgzf_crc checks it)
+              uint32_t crc0;
+              memcpy(&crc0, raw + b.in_off + b.in_size - 8, 4);
+              if (crc0 != 0) bad = 1;
+              return;
+            }
             const uint32_t xlen = raw[b.in_off + 10] | (raw[b.in_off + 11] << 8);
             z_stream& z = zs[w];
             if (!zs_init[w]) { memset(&z, 0, sizeof(z)); if (inflateInit2(&z, -15) != Z_OK) { bad = 1; return; } zs_init[w] = 1; }

@@ -458,10 +458,17 @@ int fgx_inflate_block_two_phase_host(const uint8_t* in, uint32_t in_len, uint8_t
  * written to `out`, or 0 when they do not fit `cap` (the caller stores the block). */
 uint32_t fgx_deflate_block_host(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap);
 /* The device's BGZF inflate (+ CRC-32 check) alone (fgumi_amd/csrc/bgzf_device.hip), for measurements and tests: the whole blocks of
- * raw[0 .. raw_len) go to the device once and are inflated `reps` times; *ms = device time of one pass, *inflated_len = bytes produced; with
- * `out` (inflated_cap bytes) the inflated stream comes back.  Returns 0, or non-zero with fgx_last_error(c) (a failing block is named). */
+ * raw[0 .. raw_len) go to the device once and are inflated by a warm-up pass and `reps` timed passes; *ms = device time of one timed pass,
+ * *inflated_len = bytes produced; with `out` (inflated_cap bytes) the inflated stream of the last pass comes back.  The output buffer is filled
+ * with 0xA5 before the first pass, and reps == 0 runs that first pass only (*ms = 0): the stream is then what ONE pass over poisoned memory
+ * produced (the form the tests use: a later pass into the same buffer would find the bytes of the pass before where it skipped one).
+ * Returns 0, or non-zero with fgx_last_error(c) (a failing block is named). */
 int fgx_bgzf_inflate_device_bench(fgx_caller* c, const uint8_t* raw, uint64_t raw_len, uint32_t reps, double* ms, uint64_t* inflated_len, uint8_t* out,
                                   uint64_t inflated_cap);
+/* The device's BGZF deflate alone (k_bgzf_deflate / k_bgzf_crc_write / k_bgzf_pack, what FGX_RUN_DEVICE_DEFLATE runs inside fgx_run_bam), for
+ * tests: in[0 .. len) becomes BGZF blocks of 0xff00 bytes (the last one shorter; no EOF marker), packed back to back into out[0 .. *out_len).
+ * len == 0 gives *out_len == 0.  Returns 0, or non-zero with fgx_last_error(c) — also when `cap` is too small (*out_len = bytes needed). */
+int fgx_bgzf_deflate_device_bench(fgx_caller* c, const uint8_t* in, uint64_t len, uint8_t* out, uint64_t cap, uint64_t* out_len);
 /* The host stages alone (read, inflate, deflate, write) around a copy: re-blocks a BGZF file; needs no device. */
 int fgx_bgzf_recompress_file(const char* in_path, const char* out_path, uint32_t threads, int level, uint64_t chunk_raw_bytes,
                              uint64_t* inflated_bytes);
