@@ -689,9 +689,10 @@ static int process_hybrid(fgx_caller* c, general_fn general, const uint8_t* reco
     if (rr.bytes) hip_check(hipMemcpy(c->rejects_host.data(), rr.d_out, rr.bytes, hipMemcpyDeviceToHost), "D2H rejects");
   }
   // (the rejects of EVERY group are in hand, also of the groups the device pipeline defers: the general path need not track them again)
-  struct Untrack { fgx_caller* c; uint8_t saved; Untrack(fgx_caller* cc, bool on) : c(cc), saved(cc->opt.track_rejects) { if (on) set(0); }
+  // (the device pass of a --rejects batch says so to the pipeline — fp.rejects_pass —: the deep duplex kernels stay off under --rejects, tracked here or there)
+  struct Untrack { fgx_caller* c; uint8_t saved; Untrack(fgx_caller* cc, bool on) : c(cc), saved(cc->opt.track_rejects) { if (on) { set(0); c->fast->fp.rejects_pass = saved != 0; } }
                    void set(uint8_t v) { c->opt.track_rejects = v; for (fgx_caller* w : c->workers) w->opt.track_rejects = v; }
-                   ~Untrack() { set(saved); } } untrack(c, dev_rejects || strand_rejects);
+                   ~Untrack() { set(saved); c->fast->fp.rejects_pass = false; } } untrack(c, dev_rejects || strand_rejects);
   int rc = hybrid_after_upload(c, general, records, records_len, rec_off, rec_len, n_rec, grp_first, n_grp, out, nullptr, 0);
   if (rc == 0 && strand_rejects) {
     const FastResult& fr = c->fast->last;      // (hybrid_after_upload left the device pass's result there; the uploaded records are still in d_in_*)
@@ -744,7 +745,11 @@ static bool canon_pass_enabled(const fgx_caller* c) {
 }
 static int canon_kind(const fgx_caller* c) { return c->opt.caller_kind == FGX_CALLER_CODEC ? CANON_KIND_CODEC : c->opt.caller_kind == FGX_CALLER_SIMPLEX ? CANON_KIND_SIMPLEX : CANON_KIND_DUPLEX; }
 // the runs table of the canonical batch, for the one FastPath::run that decides it
-struct RefRunsScope { FastPath& fp; RefRunsScope(FastPath& f, const void* runs) : fp(f) { fp.ref_runs = runs; } ~RefRunsScope() { fp.ref_runs = nullptr; } };
+struct RefRunsScope {   // around the `run` of a canonical second pass: its reference runs (or none), and the mark that it IS the second pass
+  FastPath& fp;
+  RefRunsScope(FastPath& f, const void* runs) : fp(f) { fp.ref_runs = runs; fp.canon_second_pass = true; }
+  ~RefRunsScope() { fp.ref_runs = nullptr; fp.canon_second_pass = false; }
+};
 
 struct CanonPass {
   std::vector<uint8_t> used;            // per deferred group: 1 = its records come from the second device pass
@@ -1500,6 +1505,7 @@ uint32_t fgx_debug_last_meth_device(const fgx_caller* c) { return (c && c->fast)
 uint32_t fgx_debug_last_meth_clipped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_meth_clipped : 0u; }
 uint32_t fgx_debug_last_deep_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_families : 0u; }
 uint32_t fgx_debug_last_wide_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_wide_families : 0u; }
+uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_duplex_deep : 0u; }
 // the split pipeline's first stage in the last device batch: out4[0] families finished by k_split_cols's packed build, [1] by its classic builds
 // (k_split_finish counts both), [2] the build launched first (0 classic alone / no split pipeline, 1 packed alone, 2 packed + partner launch),
 // [3] families the first stage handed to the next launch

@@ -1210,7 +1210,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   // simplex families go to the workgroup-per-family kernel, duplex / CODEC molecules to the general path
   auto to_retry = [&]() { if (!P.retry) { to_defer(); return; } if (lane == 0) { uint32_t k = atomicAdd(P.n_retry, 1u); P.retry[k] = g; } };
   if (!bail && n > 64) {
-    if (MODE == 0 && P.big) { if (lane == 0) { uint32_t k = atomicAdd(P.n_big, 1u); P.big[k] = g; } }   // k_family's, directly
+    if ((MODE == 0 || MODE == 1) && P.big) { if (lane == 0) { uint32_t k = atomicAdd(P.n_big, 1u); P.big[k] = g; } }   // k_family's, directly (duplex: duplex_deep.inc's list)
     else if (MODE == 0) to_retry();
     else to_defer();
     bail = true;
@@ -2841,6 +2841,7 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
 #include "simplex_seg.inc"
 #include "simplex_split.inc"
 #include "simplex_deep.inc"
+#include "duplex_deep.inc"
 #include "simplex_wide.inc"
 #include "duplex_meth.inc"
 
@@ -2994,6 +2995,7 @@ struct BatchSwitches {     // read at the start of every batch: tests and tools 
   const int split_mode = env_int(split_env, 1);
   const bool direct = env_is1(getenv("FGX_DIRECT"));                     // (tools/direct_check.py switches it between two runs of one process)
   const bool deep = env_not0(getenv("FGX_DEEP"));
+  const bool duplex_deep = env_not0(getenv("FGX_DUPLEX_DEEP"));          // 0: duplex molecules of more than 64 records are deferred, as before duplex_deep.inc
   const char* const deep_wide_env = getenv("FGX_DEEP_WIDE");
   const bool deep_wide = deep_wide_env && deep_wide_env[0] && deep_wide_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the wide kernels behind the streaming ones (simplex_wide.inc)
   const uint32_t seg_bytes = env_in(fgx_knob("FGX_SEG_BYTES"), 4096, 32768, 11776) & ~63u;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
@@ -3067,6 +3069,9 @@ struct Batch {
   // loops, the record writers' <1> builds apply the conversion-artifact rule, am/au/at, bm/bu/bt, MM/ML/cu/ct follow RX (duplex_meth.inc).
   const bool meth_dup = duplex && meth_on;
   const bool dup_cap = duplex && o.duplex_max_reads_per_strand > 0;   // the CAP builds of k_family_wave<1> and of the duplex record writers
+  // Duplex molecules of more than 64 records (duplex_deep.inc): k_family_wave<1> lists them instead of deferring them, and k_duplex_deep_parse +
+  // k_duplex_deep_cols decide the list.  Not under --trim or --rejects, not in the methylation-aware mode, not in the canonical second pass (FGX_DUPLEX_DEEP=0: off)
+  const bool dup_deep = duplex && sw.duplex_deep && !o.trim && !o.track_rejects && !fp.rejects_pass && !meth_dup && !fp.canon_second_pass;
   // Simplex without --trim: which head of the launch chain?  Shallow families (the mean family fits a quarter of a wave's LDS
   // slice) start at k_simplex_seg<4>; everything else at the split pipeline (k_split_parse + k_split_cols, simplex_split.inc),
   // whose record kernel also leaves what k_col_bound would (column bound, byte-span descriptor).
@@ -3137,6 +3142,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
+    if (!fp.canon_second_pass) fp.last_duplex_deep = 0;   // (the second pass belongs to the batch whose first pass counted)
     fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
@@ -3305,6 +3311,8 @@ struct Batch {
     // k_family's list (round 3 walked them through k_simplex_wave2 and three k_family_wave<0> launches first: 2 ms per 1 M long-tail families)
     // (not with direct records: their merge pass walks ONE list of the families that left the split pipeline — the route list)
     if (!duplex && !codec && !direct) { fp.d_big.reserve((size_t)n_grp * 4); P.big = fp.d_big.as<uint32_t>(); P.n_big = cnt(MISC_N_BIG); }
+    // duplex molecules of more than 64 records: k_family_wave<1> lists them for the kernels of duplex_deep.inc (without the list it defers them)
+    if (dup_deep) { fp.d_big.reserve((size_t)n_grp * 4); P.big = fp.d_big.as<uint32_t>(); P.n_big = cnt(MISC_N_BIG); }
     n_cur = meth_dev ? 0u : n_grp;       // (methylation-aware mode: no wavefront-per-family kernel runs)
   }
 
@@ -3324,8 +3332,15 @@ struct Batch {
       FastParams PS = stage_params(st[i].bytes, i + 1 < st.size() || keep_last);
       launch(st[i], PS);
       uint32_t n_next = 0;
-      hip_check(hipMemcpyAsync(&n_next, cnt(MISC_N_RETRY), 4, hipMemcpyDeviceToHost, s), "D2H");
-      sync();
+      if (dup_deep) {   // the count of listed deep molecules travels with the copy the chain waits for anyway (the split stages' window: retry .. big)
+        unsigned long long h_cnt[MISC_SPLIT_WINDOW] = {};
+        hip_check(hipMemcpyAsync(h_cnt, misc + MISC_N_RETRY, sizeof(h_cnt), hipMemcpyDeviceToHost, s), "D2H");
+        sync();
+        n_next = (uint32_t)h_cnt[0]; n_dup_deep = (uint32_t)h_cnt[MISC_N_BIG - MISC_N_RETRY];
+      } else {
+        hip_check(hipMemcpyAsync(&n_next, cnt(MISC_N_RETRY), 4, hipMemcpyDeviceToHost, s), "D2H");
+        sync();
+      }
       next_list(PS.retry ? n_next : 0);
     }
   }
@@ -3544,6 +3559,37 @@ struct Batch {
       else FGX_LAUNCH(HIP_KERNEL_NAME(k_family_wave<0>), grid, block, lds, s, PS, n_cur);
     });
     if (meth_dup) fp.last_meth_device = n_grp;
+  }
+
+  // ---- deep duplex molecules (duplex_deep.inc): the list k_family_wave<1> filled — sizes, scan, the record kernel in its two builds, the column kernel.
+  //      What they do not take is on the deferred list when they are done.  A batch without such a molecule launches nothing and waits for nothing here ----
+  uint32_t n_dup_deep = 0;   // listed molecules (run_slices reads the count); not counted into last_big_families / last_deep_families: those are the simplex path's
+  bool dup_deep_ran = false;
+  void duplex_deep_molecules() {
+    if (!dup_deep || !n_dup_deep) return;
+    const uint32_t* const list = fp.d_big.as<uint32_t>();
+    const uint32_t n_list = n_dup_deep;
+    fp.d_deep_sizes.reserve((size_t)n_list * 8 + 64); fp.d_deep_row0.reserve((size_t)n_list * 8 + 64);
+    FGX_LAUNCH(k_deep_sizes, dim3((n_list + 255) / 256), dim3(256), 0, s, list, n_list, d_grp_first, fp.d_deep_sizes.as<uint64_t>());
+    scan_u64(fp.d_deep_sizes.as<uint64_t>(), fp.d_deep_row0.as<uint64_t>(), n_list, "scan of the deep molecules' records");
+    uint64_t lastr[2] = {0, 0};
+    hip_check(hipMemcpyAsync(&lastr[0], fp.d_deep_row0.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&lastr[1], fp.d_deep_sizes.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    const uint64_t n_rows = lastr[0] + lastr[1];
+    if (n_rows > (uint64_t)n_rec) throw std::runtime_error("device pipeline: " + std::to_string(n_rows) + " rows for the deep duplex kernels, more than the batch has records");
+    fp.d_deep_rows.reserve((size_t)n_rows * sizeof(DeepRow) + 64); fp.d_deep_fams.reserve((size_t)n_list * sizeof(DuplexDeepMol) + 64);
+    hip_check(hipMemsetAsync(cnt(MISC_N_DEEP), 0, 4, s), "memset");
+    DuplexDeepParams DP;
+    DP.list = list; DP.n_list = n_list; DP.row0 = fp.d_deep_row0.as<uint64_t>();
+    DP.rows = fp.d_deep_rows.as<DeepRow>(); DP.mols = fp.d_deep_fams.as<DuplexDeepMol>(); DP.n_done = cnt(MISC_N_DEEP);
+    FastParams PD = P;
+    PD.group_list = nullptr;
+    // (both builds over the whole list: a workgroup whose molecule is the other build's returns at once)
+    FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
+    FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    FGX_LAUNCH(k_duplex_deep_cols, dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
+    dup_deep_ran = true;   // (the count of decided molecules comes back with the batch's counters)
   }
 
   // ---- deep families: k_deep_parse + k_deep_cols (simplex_deep.inc) take the big list; what is outside their shape goes on to k_family ----
@@ -3861,6 +3907,7 @@ struct Batch {
     for (int i = 0; i < FGX_STATS_LEN; i++) res->stats[i] = h_misc[MISC_STATS + i];
     res->n_deferred = (uint32_t)(h_misc[MISC_N_DEFERRED] & 0xFFFFFFFFull);
     fp.last_meth_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] & 0xFFFFFFFFull);
+    if (dup_deep_ran) fp.last_duplex_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull);
     res->d_deferred = fp.d_deferred.as<uint32_t>();
     res->d_out_off = fp.d_offsets.as<uint64_t>();
     res->d_slot_size = fp.d_sizes.as<uint64_t>();
@@ -3889,6 +3936,7 @@ int run_once(FastPath& fp, fgx_caller* c, const uint8_t* d_blob, uint64_t blob_l
   if (b.use_split) b.split_pipeline();
   if (b.simplex_v2) b.wave2_chain();
   b.family_wave_stages();
+  b.duplex_deep_molecules();
   b.deep_families();
   b.workgroup_families();
   if (const int rc = b.call_full()) return rc;

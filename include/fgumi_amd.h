@@ -473,6 +473,10 @@ int fgx_bgzf_deflate_device_bench(fgx_caller* c, const uint8_t* in, uint64_t len
 int fgx_bgzf_recompress_file(const char* in_path, const char* out_path, uint32_t threads, int level, uint64_t chunk_raw_bytes,
                              uint64_t* inflated_bytes);
 const char* fgx_pipeline_last_error(void);
+/* Diagnostics of the last device batch of `c`: duplex molecules of more than 64 records that the streaming duplex kernels
+ * (fgumi_amd/csrc/duplex_deep.inc: k_duplex_deep_parse + k_duplex_deep_cols) decided — up to 512 records, at most 255 retained reads per record
+ * side; FGX_DUPLEX_DEEP=0 turns the path off and such molecules are deferred to the general path.  0 for a caller that has run no device batch. */
+uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c);
 
 /* Sizes for a parameter set: total blob bytes (records WITH block_size prefixes) and record count. */
 int fgx_sim_sizes(const fgx_sim_params* p, uint64_t* blob_len, uint64_t* n_rec);
