@@ -1506,6 +1506,7 @@ uint32_t fgx_debug_last_meth_clipped(const fgx_caller* c) { return (c && c->fast
 uint32_t fgx_debug_last_deep_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_families : 0u; }
 uint32_t fgx_debug_last_wide_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_wide_families : 0u; }
 uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_duplex_deep : 0u; }
+uint32_t fgx_debug_last_duplex_deep_capped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_duplex_deep_capped : 0u; }
 // the split pipeline's first stage in the last device batch: out4[0] families finished by k_split_cols's packed build, [1] by its classic builds
 // (k_split_finish counts both), [2] the build launched first (0 classic alone / no split pipeline, 1 packed alone, 2 packed + partner launch),
 // [3] families the first stage handed to the next launch

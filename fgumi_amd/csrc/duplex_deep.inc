@@ -28,10 +28,19 @@
 //     assumes; no new record writer is needed;
 //   * a consensus UMI character sees the reads of one side that carry RX: its four counts are bytes of an item too.
 // A molecule holds at most DEEP_MAX = 512 records (510 retained reads at the bound; the LDS arrays of the record kernel).
+// A --max-reads-per-strand does not move the bound: the 255 count ALL retained reads of a side, scoring or not — col_obs_all (the recount of a capped
+// molecule) and the consensus UMI's item counts are bytes over every source read, whatever the cap leaves for the columns.  DEEP_MAX stays 512.
+//
+// --max-reads-per-strand (the CAP builds, k_duplex_deep_parse<NT, MAXR, 1> + k_duplex_deep_cols<1>; launched for a caller with a cap > 0 under
+// FGX_DUPLEX_DEEP_CAP=1): a set above the cap is scored over its `cap` lowest fgbio name ranks, ties in file order, and the scoring reads enter a column in
+// that order.  The record kernel keeps the rows of every retained read in file order and adds, for a capped set, COPIES of its scoring rows in walk order
+// (DuplexDeepParams::rows_walk, at the set's place) — copies, not a list of indices into the file-order rows: the column loop's row loads are scalar loads
+// of 32 consecutive bytes at `base + 32 j`, issued a batch ahead of their use, and an index list would put a second, dependent scalar load in front of each
+// of them (load the index, wait, load the row), while the copies cost one more 32-byte store per scoring read in a kernel that already writes the row.
 //
 // Outside the shape — the molecule leaves for the deferred list, as it did from k_family_wave<1>: an indel or a clip (more than one CIGAR op), a secondary or
 // supplementary record, an unmapped read, an MC the closed-form mate clip does not take, no `/A` | `/B` on a paired record, absent qualities, a paired
-// record that is FIRST and LAST, a --max-reads-per-strand that bites a set, a side above the bound, more than DEEP_MAX records, RX of unequal length or
+// record that is FIRST and LAST, a --max-reads-per-strand that bites a set (without the CAP builds, and a cap of 0 with them), a side above the bound, more than DEEP_MAX records, RX of unequal length or
 // above FAST_RX_CAP, an IUPAC code in a lone read, an overflow of the FullItem pool.  The host launches nothing of this under --trim, --rejects, in the
 // methylation-aware mode or in the canonical second pass.
 
@@ -51,7 +60,10 @@ struct DuplexDeepMol {      // 96 bytes: what k_duplex_deep_parse hands to k_dup
   uint32_t fp, fc;          // first paired record (MI -> read name, MI tag) and first /A (else /B) paired record (cell barcode), indices inside the molecule
   uint16_t mi_off, cb_off;  // ... their values' offsets inside the record body
   uint8_t mi_len, cb_len, has_cb, _pad0;   // mi_len: without the `/A` | `/B`
-  uint32_t _pad[5];
+  // the CAP builds (--max-reads-per-strand; zero from the others): the SCORING reads of each set — the whole set unless the cap bites it
+  uint16_t sc[4];           // how many: min(m, cap)
+  uint16_t slen[4];         // the longest of them: the length of the set's consensus
+  uint32_t capped;          // bit k: the cap bites set k (its scoring rows, in walk order, are in DuplexDeepParams::rows_walk)
 };
 static_assert(sizeof(DuplexDeepMol) == 96, "duplex deep descriptor");
 
@@ -59,7 +71,8 @@ struct DuplexDeepParams {
   const uint32_t* list; uint32_t n_list;     // the molecules of more than 64 records
   const uint64_t* row0;                      // per list entry: first DeepRow (exclusive scan of the record counts)
   DeepRow* rows; DuplexDeepMol* mols;        // mols: per list entry
-  uint32_t* n_done;                          // molecules these kernels decided (fgx_debug_last_duplex_deep)
+  uint32_t* n_done;                          // molecules these kernels decided (fgx_debug_last_duplex_deep); [1]: of which the cap bit (fgx_debug_last_duplex_deep_capped)
+  DeepRow* rows_walk;                        // the CAP builds: copies of a capped set's scoring rows in (rank, file order), at the set's place in `rows`
 };
 
 // DeepRow::w[7] of a duplex row: bit 2 of the flags byte = the read's FIRST flag (the halves of a paired UMI are flipped for reads whose FIRST flag differs
@@ -78,7 +91,7 @@ struct DuplexDeepLds : DeepLds<MAXR> {
 // <NT, MAXR>: <128, 128> takes the listed molecules of up to 128 records, <256, DEEP_MAX> the larger ones — both are launched over the whole list and a
 // workgroup whose molecule is the other build's returns at once (no hand-over list, no host synchronisation between them).  Thread = record: a 66-record
 // molecule in the 256-thread build would leave three of its four wavefronts without a record (DESIGN.md §4 has the figures).
-template <uint32_t NT, uint32_t MAXR>
+template <uint32_t NT, uint32_t MAXR, int CAP = 0>
 __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDeepParams D) {
   __shared__ DuplexDeepLds<MAXR> S;
   __shared__ __align__(16) uint8_t sTagCls[256];
@@ -239,11 +252,62 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
     if (!same1 || !same2) { status = 1; rj_coll = n_ab; }
   }
   const uint32_t m0 = S.set_rem[0], m1 = S.set_rem[1], m2 = S.set_rem[2], m3 = S.set_rem[3];
+  uint32_t cutm = 0;                                                     // (CAP) bit k: the cap bites set k
+  uint32_t la0 = 0, la1 = 0, la2 = 0, la3 = 0;                           // (CAP) the longest retained read of each set, ahead of the cap
   if (status == 2) {
-    // a --max-reads-per-strand that bites a set: the general path (a cap that does not bite changes nothing); a side above the bound likewise
+    // a --max-reads-per-strand that bites a set: the general path without the CAP build, and with a cap of 0 (no set has a consensus); a cap that does
+    // not bite changes nothing.  A side above the bound likewise — whatever the cap: the bound counts ALL retained reads ("The bound" above)
     const uint32_t mx = (m0 > m1 ? m0 : m1) > (m2 > m3 ? m2 : m3) ? (m0 > m1 ? m0 : m1) : (m2 > m3 ? m2 : m3);
-    if (P.dmax_reads >= 0 && (long long)mx > P.dmax_reads) { leave(); return; }
+    if (P.dmax_reads >= 0 && (long long)mx > P.dmax_reads) {
+      if (CAP == 0 || P.dmax_reads == 0) { leave(); return; }
+      const uint32_t cap = (uint32_t)P.dmax_reads;
+      cutm = (m0 > cap ? 1u : 0u) | (m1 > cap ? 2u : 0u) | (m2 > cap ? 4u : 0u) | (m3 > cap ? 8u : 0u);
+    }
     if (m0 + m3 > DUPLEX_DEEP_SIDE_MAX || m1 + m2 > DUPLEX_DEEP_SIDE_MAX) { leave(); return; }
+  }
+  // --max-reads-per-strand (consensus_call, vanilla_caller.rs:706-779 with downsample_source_reads :970-980; k_family_wave<1, 0, 1> restates it for a
+  // wavefront, k_deep_parse's ranks for a workgroup): a set above the cap is SCORED over its `cap` lowest fgbio name ranks, ties in file order, and the
+  // scoring reads enter a column in that order.  `key` is done with as the pairing hash: it holds the rank of each retained read of a capped set, then the
+  // read's place in the walk order (a place >= cap: not a scoring read).  set_len of a capped set becomes the longest SCORING read.  Everything else of the
+  // molecule keeps the whole set and file order — the rows below, and through them the consensus UMI and the recount's all-reads counts.
+  // (Workgroup-uniform — cutm comes from LDS every thread read alike; a molecule the cap does not bite runs nothing of this.)
+  if constexpr (CAP != 0) {
+    la0 = S.set_len[0]; la1 = S.set_len[1]; la2 = S.set_len[2]; la3 = S.set_len[3];
+    if (cutm) {
+      const uint32_t cap = (uint32_t)P.dmax_reads;
+      auto cut_set = [&](uint32_t r) -> int {                            // the capped set record r is a retained read of, or -1
+        const uint32_t d = S.dup[r];
+        if (!(d & 4u) || S.final_len[r] == 0) return -1;
+        const uint32_t k = ((d & 3u) - 1u) * 2u + ((d & 8u) ? 0u : 1u);
+        return ((cutm >> k) & 1u) ? (int)k : -1;
+      };
+      for (uint32_t r = tid; r < n; r += NT)
+        if (cut_set(r) >= 0) S.key[r] = (uint32_t)name_rank(P.blob + S.off[r] + 32, S.name_len[r]);
+      __syncthreads();
+      uint32_t place[MAXR / NT];                                         // of record tid + i * NT
+#pragma unroll
+      for (uint32_t i = 0; i < MAXR / NT; i++) {
+        const uint32_t r = tid + i * NT;
+        place[i] = 0xFFFFFFFFu;
+        if (r >= n || cut_set(r) < 0) continue;
+        const uint32_t dk = S.dup[r] & 15u;                              // (strand, paired, FIRST): the set
+        const int32_t rk = (int32_t)S.key[r];
+        uint32_t before = 0;
+        for (uint32_t j = 0; j < n; j++) {
+          if ((S.dup[j] & 15u) != dk || S.final_len[j] == 0) continue;
+          const int32_t rj = (int32_t)S.key[j];
+          before += (rj < rk || (rj == rk && j < r)) ? 1u : 0u;
+        }
+        place[i] = before;
+      }
+      __syncthreads();
+      if (tid < 4 && ((cutm >> tid) & 1u)) S.set_len[tid] = 0;           // (every thread read them, barriers ago)
+#pragma unroll
+      for (uint32_t i = 0; i < MAXR / NT; i++) { const uint32_t r = tid + i * NT; if (r < n && place[i] != 0xFFFFFFFFu) S.key[r] = place[i]; }
+      __syncthreads();
+      for (uint32_t r = tid; r < n; r += NT) { const int k = cut_set(r); if (k >= 0 && S.key[r] < cap) atomicMax(&S.set_len[k], (uint32_t)S.final_len[r]); }
+      __syncthreads();
+    }
   }
 
   // ---- 5. member rows: set 0's retained reads, then set 1's, 2's, 3's, file order inside a set -----------------------------------------------------------
@@ -270,6 +334,7 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
       R.w[7] = ((hrx ? (uint32_t)S.rx_rel[r] - (uint32_t)S.seq_rel[r] : 0u) & 0xFFFFu) |
                ((((S.bits[r] & 4u) ? 1u : 0u) | (hrx ? 2u : 0u) | ((d & 8u) ? 4u : 0u)) << 16) | ((uint32_t)S.rx_len[r] << 24);
       D.rows[row0 + row] = R;
+      if constexpr (CAP != 0) { if (((cutm >> k) & 1u) && S.key[r] < (uint32_t)P.dmax_reads) D.rows_walk[row0 + (row - rank) + S.key[r]] = R; }
     }
   }
 
@@ -280,6 +345,12 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
     f.status = status; f.n = n; f.row0 = (uint32_t)row0;
     f.m[0] = (uint16_t)m0; f.m[1] = (uint16_t)m1; f.m[2] = (uint16_t)m2; f.m[3] = (uint16_t)m3;
     for (int k = 0; k < 4; k++) f.elen[k] = (uint16_t)S.set_len[k];
+    if constexpr (CAP != 0) {
+      const uint32_t cap = (uint32_t)P.dmax_reads;
+      for (int k = 0; k < 4; k++) { f.slen[k] = f.elen[k]; f.sc[k] = ((cutm >> k) & 1u) ? (uint16_t)cap : f.m[k]; }
+      f.elen[0] = (uint16_t)la0; f.elen[1] = (uint16_t)la1; f.elen[2] = (uint16_t)la2; f.elen[3] = (uint16_t)la3;
+      f.capped = cutm;
+    }
     f.n_frag = n_frag; f.n_ab = n_ab; f.n_zero = S.n_zero; f.rj_insuf = rj_insuf; f.rj_coll = rj_coll;
     f.ov_agree = S.ov_agree; f.ov_dis = S.ov_dis; f.ov_corr = S.ov_corr;
     if (n_ab) {
@@ -298,6 +369,11 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
 #ifndef FGX_DUPLEX_DEEP_OCC
 #define FGX_DUPLEX_DEEP_OCC 8
 #endif
+// <CAP>: the build for a caller with --max-reads-per-strand.  A capped set's columns come from its SCORING rows in walk order (rows_walk) — bases, qualities,
+// col_err, col_obs, the depth maxima, the set's length and so the lengths of the records; a scoring set of one read takes the single-read table —, then its
+// columns once more over EVERY row of the set, counting only (col_obs_all: the duplex error recount works from source_reads, which the cap does not touch);
+// an uncapped set of such a molecule copies col_obs there.  The consensus UMI keeps all rows of a side in file order.  CAP 0: none of it.
+template <int CAP>
 __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(FastParams P, DuplexDeepParams D) {
   __shared__ __align__(16) FwLds sL;
   ConsensusTables& sT = sL.t;
@@ -319,6 +395,8 @@ __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(F
   const uint32_t n = uni(Mp->n), n_frag = uni(Mp->n_frag), n_ab = uni(Mp->n_ab), n_zero = uni(Mp->n_zero);
   const uint32_t r0 = uni(P.grp_first[g]);
   const uint32_t slot0 = 3 * g;
+  uint32_t cmask = 0;                                                     // bit k: the cap bites set k
+  if constexpr (CAP != 0) cmask = uni(Mp->capped);
   unsigned long long* const st = P.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * 32;
   uint32_t s_cons = 0, s_filtered = n_frag, rj_insuf = 0, rj_coll = 0, rj_zero = 0;
   auto flush_stats = [&]() {
@@ -336,6 +414,7 @@ __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(F
       if (ov_dis) atomicAdd(&st[26], (unsigned long long)ov_dis);
       if (ov_corr) atomicAdd(&st[27], (unsigned long long)ov_corr);
       atomicAdd(D.n_done, 1u);
+      if constexpr (CAP != 0) { if (cmask) atomicAdd(D.n_done + 1, 1u); }
     }
   };
   auto to_defer = [&]() { if (lane == 0) { const uint32_t k = atomicAdd(P.n_deferred, 1u); P.deferred[k] = g; } };
@@ -345,7 +424,10 @@ __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(F
     return;
   }
   const uint32_t ms0 = uni(Mp->m[0]), ms1 = uni(Mp->m[1]), ms2 = uni(Mp->m[2]), ms3 = uni(Mp->m[3]);
-  const uint32_t el0 = uni(Mp->elen[0]), el1 = uni(Mp->elen[1]), el2 = uni(Mp->elen[2]), el3 = uni(Mp->elen[3]);
+  // the scoring reads of each set and the length of its consensus, their longest (CAP: k_duplex_deep_parse<.., 1> fills sc / slen for every molecule)
+  const uint32_t sc0 = CAP != 0 ? uni(Mp->sc[0]) : ms0, sc1 = CAP != 0 ? uni(Mp->sc[1]) : ms1, sc2 = CAP != 0 ? uni(Mp->sc[2]) : ms2, sc3 = CAP != 0 ? uni(Mp->sc[3]) : ms3;
+  const uint32_t el0 = uni(CAP != 0 ? Mp->slen[0] : Mp->elen[0]), el1 = uni(CAP != 0 ? Mp->slen[1] : Mp->elen[1]), el2 = uni(CAP != 0 ? Mp->slen[2] : Mp->elen[2]),
+                 el3 = uni(CAP != 0 ? Mp->slen[3] : Mp->elen[3]);
   auto pick = [](uint32_t k, uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return k == 0 ? a : k == 1 ? b : k == 2 ? c : d; };
   const uint32_t plen1 = (ms0 && ms3) ? (el0 < el3 ? el0 : el3) : 0;    // R1 duplex: AB-R1 with BA-R2
   const uint32_t plen2 = (ms1 && ms2) ? (el1 < el2 ? el1 : el2) : 0;    // R2 duplex: AB-R2 with BA-R1
@@ -372,11 +454,64 @@ __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(F
   uint32_t dtr0 = 0, dtr1 = 0, dtr2 = 0, dtr3 = 0, dfu0 = 0, dfu1 = 0, dfu2 = 0, dfu3 = 0;   // max depth over the paired span / the whole strand, per set
   bool odd_base = false;
   uint32_t row_base = 0, coff = 0;
+  // (CAP) the count-only pass of a capped set: one 64-column pass (columns p0s .. p0s + 63 of a set of length Lc) over the `m` rows at `er`, FGX_DEEP_BATCH at a
+  // time; `see(valid, code)` once per row and lane — valid: inside the read's final length, not masked, one of A C G T, after the overlapping-bases
+  // pre-correction and the strand complement.  It is the batch of the column loop below, loads and masking rule, without the chains: the column loop keeps
+  // its own copy, because handing it the batch through this lambda cost the CAP 0 build registers (DESIGN.md §3 has the figures).
+  auto stream_rows = [&](const RowPtr er, const uint32_t m, const uint32_t p0s, const uint32_t p, const uint32_t Lc, auto&& see) {
+    const uint32_t shp = (~p & 1u) << 2;                       // nibble shift of an even / odd index (a reverse read of even length flips it)
+    constexpr int NB = FGX_DEEP_BATCH;
+    for (uint32_t j0 = 0; j0 < m; j0 += NB) {
+      u32x8 R_[NB];
+#pragma unroll
+      for (int t = 0; t < NB; t++) R_[t] = er[uni(j0 + t < m ? j0 + t : m - 1u)];   // (past the end: the last row again, not observed)
+      uint32_t b_[NB], q_[NB], b2_[NB], q2_[NB], d_[NB];
+      bool in_[NB];
+      // every load of the batch is issued before the first of them is used
+#pragma unroll
+      for (int t = 0; t < NB; t++) {
+        const u32x8& R = R_[t];
+        const uint32_t L = R[4] & 0xFFFFu, fin = R[4] >> 16;
+        const bool rv = ((R[7] >> 16) & 1u) != 0;
+        const uint32_t lim = fin < Lc ? fin : Lc;          // inside the read's final length AND a column of the set
+        in_[t] = p < lim && (j0 + t < m);
+        const uint32_t xm = rv ? ~0u : 0u, xk = rv ? L : 0u;    // index into the read: forward p, reverse L - 1 - p = (p ^ ~0) + L
+        const uint32_t ix = in_[t] ? (p ^ xm) + xk : 0u;
+        const uint8_t* const sq = row_seq(R);
+        b_[t] = sq[ix >> 1]; q_[t] = sq[((L + 1u) >> 1) + ix];
+        b2_[t] = 0; q2_[t] = 0; d_[t] = 0xFFFFFFFFu;
+        const uint32_t wo = R[5] >> 16, wc = R[6] >> 16;
+        // the row shares positions with its mate inside THIS pass's window of indices (all scalar)
+        const int32_t lo = rv ? (int32_t)L - 64 - (int32_t)p0s : (int32_t)p0s;
+        if (wc != 0 && lo < (int32_t)(wo + wc) && lo + 63 >= (int32_t)wo) {
+          const uint32_t d = ix - wo, mo = R[6] & 0xFFFFu, mL = R[5] & 0xFFFFu;
+          const bool hit = in_[t] && d < wc;
+          const uint32_t j = hit ? mo + d : 0u;
+          const uint8_t* const sm = row_mate(R);
+          b2_[t] = sm[j >> 1]; q2_[t] = sm[((mL + 1u) >> 1) + j];
+          d_[t] = hit ? j : 0xFFFFFFFFu;                  // (the mate's index: its parity picks the nibble)
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < NB; t++) {
+        const u32x8& R = R_[t];
+        const bool rv = ((R[7] >> 16) & 1u) != 0;
+        const uint32_t L = R[4] & 0xFFFFu;
+        uint32_t c = __builtin_amdgcn_ubfe(b_[t], shp ^ ((rv && !(L & 1u)) ? 4u : 0u), 4u), q = q_[t];   // parity of L - 1 - p = parity of p when L is odd
+        if (d_[t] != 0xFFFFFFFFu) deep_correct(c, q, __builtin_amdgcn_ubfe(b2_[t], (~d_[t] & 1u) << 2, 4u), q2_[t]);
+        if (rv) c = __builtin_bitreverse32(c) >> 28;       // complement = bit reversal of the code
+        const bool valid = in_[t] && q >= min_bq && __builtin_amdgcn_ubfe(0x116u, c, 1u) != 0;   // inside the read, not masked, one of A C G T
+        see(valid, c);
+      }
+    }
+  };
 #pragma unroll 1
   for (uint32_t k = 0; k < 4; k++) {
-    const uint32_t m = pick(k, ms0, ms1, ms2, ms3), Lc = pick(k, el0, el1, el2, el3);
+    const uint32_t m = pick(k, sc0, sc1, sc2, sc3), Lc = pick(k, el0, el1, el2, el3);      // the SCORING reads (CAP 0: sc is ms)
     const uint32_t plen = (k == 0 || k == 3) ? plen1 : plen2;
-    const RowPtr er = (RowPtr)(rows + row_base);
+    const bool by_rank = CAP != 0 && ((cmask >> k) & 1u) != 0;     // a capped set: its scoring rows in (rank, file order), from rows_walk
+    const bool copy_all = CAP != 0 && cmask != 0 && !by_rank;      // an uncapped set beside a capped one: col_obs IS the count over every source read
+    const RowPtr er = (RowPtr)((by_rank ? D.rows_walk + uni(Mp->row0) : rows) + row_base);
     uint32_t lfu = 0, ltr = 0;
     if (m == 1) {   // single-read consensus: LUT keyed by the unclamped quality (vanilla_caller.rs:1677-1708)
       const u32x8 R = er[0];
@@ -400,6 +535,7 @@ __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(F
         const uint32_t depth = code != 15 ? 1u : 0u;
         if (depth && !(o0 | o1 | o2 | o3)) odd_base = true;               // IUPAC code in a lone read: general path
         P.col_obs[o] = o0 | (o1 << 8) | (o2 << 16) | (o3 << 24);
+        if constexpr (CAP != 0) { if (copy_all) P.col_obs_all[o] = o0 | (o1 << 8) | (o2 << 16) | (o3 << 24); }
         lfu = depth > lfu ? depth : lfu;
         if (p < plen) ltr = depth > ltr ? depth : ltr;
       }
@@ -476,14 +612,30 @@ __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(F
             P.col_code[o] = ob; P.col_qual[o] = oq; P.col_err[o] = (uint16_t)err;
           }
           P.col_obs[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24);     // (a set is part of a side: every count <= 255)
+          if constexpr (CAP != 0) { if (copy_all) P.col_obs_all[o] = obs[0] | (obs[1] << 8) | (obs[2] << 16) | (obs[3] << 24); }
           lfu = depth > lfu ? depth : lfu;
           if (p < plen) ltr = depth > ltr ? depth : ltr;
         }
       }
     }
+    // A capped set's columns once more, counting only: the observations of EVERY retained read of the set (the scoring ones included; file order, which
+    // a count does not see) — what the duplex error recount of the record writers works from.  (uniform trip counts: m_all and Lc are scalars)
+    if constexpr (CAP != 0) {
+      if (by_rank) {
+        const uint32_t m_all = pick(k, ms0, ms1, ms2, ms3);
+        const RowPtr ar = (RowPtr)(rows + row_base);
+        for (uint32_t p0 = 0; p0 < Lc; p0 += 64) {
+          const uint32_t p0s = uni(p0);
+          const uint32_t p = p0s + lane;
+          uint32_t cnt = 0;
+          stream_rows(ar, m_all, p0s, p, Lc, [&](bool valid, uint32_t c) { cnt += valid ? 1u << (c == 1u ? 0u : c == 2u ? 8u : c == 4u ? 16u : 24u) : 0u; });
+          if (p < Lc) P.col_obs_all[col_base + coff + p] = cnt;
+        }
+      }
+    }
     lfu = uni(wave_max(lfu)); ltr = uni(wave_max(ltr));
     if (k == 0) { dfu0 = lfu; dtr0 = ltr; } else if (k == 1) { dfu1 = lfu; dtr1 = ltr; } else if (k == 2) { dfu2 = lfu; dtr2 = ltr; } else { dfu3 = lfu; dtr3 = ltr; }
-    row_base += m; coff += Lc;
+    row_base += pick(k, ms0, ms1, ms2, ms3); coff += Lc;            // (the rows of a set: ALL its retained reads)
   }
   if (__any(odd_base)) { to_defer(); return; }
 
@@ -622,7 +774,7 @@ __global__ __launch_bounds__(256, FGX_DUPLEX_DEEP_OCC) void k_duplex_deep_cols(F
         Dd->mi_off = Mp->mi_off; Dd->mi_len = (uint8_t)fp_mi_len;
         Dd->has_cb = fc_has_cb ? 1 : 0; Dd->cb_off = Mp->cb_off; Dd->cb_len = (uint8_t)fc_cb_len;
         Dd->has_rx = cnt > 0; Dd->rx_len = (uint8_t)ulen; Dd->type = (uint8_t)(1 + t); Dd->has_ba = O.has_ba ? 1 : 0;
-        Dd->meth = 0; Dd->capped = 0;
+        Dd->meth = 0; Dd->capped = (CAP != 0 && cmask != 0) ? 1 : 0;
         const uint32_t nm = P.prefix_len + 1 + fp_mi_len;
         const uint32_t per_strand = P.per_base_tags ? 2 * (3 + L + 1) + 2 * (8 + 2 * L) : 0;     // ac/aq strings + ad/ae arrays
         // every int tag holds a depth <= DUPLEX_DEEP_SIDE_MAX (a byte: c or C): 4 bytes each

@@ -2921,7 +2921,7 @@ __global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, uns
 void FastPath::release() {
   for (DevBuf* b : {&d_ends, &d_sizes, &d_offsets, &d_code, &d_qual, &d_depth, &d_err, &d_misc, &d_deferred, &d_out, &d_scan_tmp, &d_strings, &d_obs, &d_obs_all, &d_retry2,
                     &d_retry, &d_bound, &d_colbase, &d_statslots, &d_full_items, &d_full_count, &d_full_res, &d_full_flag, &d_retry_old, &d_w2img, &d_famdesc, &d_fwimg,
-                    &d_split_rec, &d_split_fam, &d_split_out, &d_route, &d_s2img, &d_dir_size, &d_dir_off, &d_dir_base, &d_slot_desc, &d_slot_err, &d_out2, &d_scan_tmp2, &d_big, &d_deep_sizes, &d_deep_row0, &d_deep_rows, &d_deep_fams, &d_deep_out, &d_deep_out2, &d_wide_scratch, &d_wide_pass, &d_wide_pass0, &d_wide_depth, &d_mflag, &d_mu, &d_mt, &d_mslot, &d_mcontigs})
+                    &d_split_rec, &d_split_fam, &d_split_out, &d_route, &d_s2img, &d_dir_size, &d_dir_off, &d_dir_base, &d_slot_desc, &d_slot_err, &d_out2, &d_scan_tmp2, &d_big, &d_deep_sizes, &d_deep_row0, &d_deep_rows, &d_deep_walk, &d_deep_fams, &d_deep_out, &d_deep_out2, &d_wide_scratch, &d_wide_pass, &d_wide_pass0, &d_wide_depth, &d_mflag, &d_mu, &d_mt, &d_mslot, &d_mcontigs})
     b->free_();
   for (int i = 0; i < 4; i++) if (ev[i]) { (void)hipEventDestroy(ev[i]); ev[i] = nullptr; }
   if (s2) {
@@ -2946,7 +2946,7 @@ enum MiscWord : uint32_t {
   MISC_SMALL_RECS = 35,      // records in families of at most 64 records (k_col_bound)
   MISC_DIR_FLAGS = 36,       // direct records: low half families whose records differ in size from the prediction, high half records past the room
   MISC_N_BIG = 37,           // families of more than 64 records: k_family's list
-  MISC_N_DEEP = 38,          // families a pass of the streaming kernels hands on
+  MISC_N_DEEP = 38,          // families a pass of the streaming kernels hands on; duplex_deep.inc: low half the molecules it decided, high half those of them a strand cap bit
   MISC_BUILD_FAMILIES = 40,  // [40, 44): the slots' diagnostics (k_reduce_stats): families finished by k_split_cols's packed build, by its classic builds, by the packed build's clean / general row loop
   MISC_N_SLOW = 44,          // duplex / CODEC: records the fast writer leaves to the per-field kernel
   MISC_FULL_RESULTS = 46,    // [46, 51): items answered through the result array, items scattered, families the writer applies, families refused as not in one piece, families refused for more than 64 items
@@ -2998,6 +2998,8 @@ struct BatchSwitches {     // read at the start of every batch: tests and tools 
   const bool duplex_deep = env_not0(getenv("FGX_DUPLEX_DEEP"));          // 0: duplex molecules of more than 64 records are deferred, as before duplex_deep.inc
   const char* const deep_wide_env = getenv("FGX_DEEP_WIDE");
   const bool deep_wide = deep_wide_env && deep_wide_env[0] && deep_wide_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the wide kernels behind the streaming ones (simplex_wide.inc)
+  const char* const duplex_deep_cap_env = getenv("FGX_DUPLEX_DEEP_CAP");
+  const bool duplex_deep_cap = duplex_deep_cap_env && duplex_deep_cap_env[0] && duplex_deep_cap_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the CAP builds of duplex_deep.inc
   const uint32_t seg_bytes = env_in(fgx_knob("FGX_SEG_BYTES"), 4096, 32768, 11776) & ~63u;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
   const uint32_t wave_bytes = env_in(fgx_knob("FGX_WAVE_BYTES"), 1024, 22016, 0) & ~15u;     // tuning knobs (0: the FastPath's own value)
   const uint32_t lds_tile_large = env_in(fgx_knob("FGX_LDS_TILE_LARGE"), 16384, 163840, 0) & ~15u;
@@ -3072,6 +3074,8 @@ struct Batch {
   // Duplex molecules of more than 64 records (duplex_deep.inc): k_family_wave<1> lists them instead of deferring them, and k_duplex_deep_parse +
   // k_duplex_deep_cols decide the list.  Not under --trim or --rejects, not in the methylation-aware mode, not in the canonical second pass (FGX_DUPLEX_DEEP=0: off)
   const bool dup_deep = duplex && sw.duplex_deep && !o.trim && !o.track_rejects && !fp.rejects_pass && !meth_dup && !fp.canon_second_pass;
+  // ... and their CAP builds, which decide a --max-reads-per-strand that bites a set of such a molecule (FGX_DUPLEX_DEEP_CAP=1; off: it is deferred)
+  const bool dup_deep_cap = dup_deep && dup_cap && sw.duplex_deep_cap;
   // Simplex without --trim: which head of the launch chain?  Shallow families (the mean family fits a quarter of a wave's LDS
   // slice) start at k_simplex_seg<4>; everything else at the split pipeline (k_split_parse + k_split_cols, simplex_split.inc),
   // whose record kernel also leaves what k_col_bound would (column bound, byte-span descriptor).
@@ -3142,7 +3146,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
-    if (!fp.canon_second_pass) fp.last_duplex_deep = 0;   // (the second pass belongs to the batch whose first pass counted)
+    if (!fp.canon_second_pass) fp.last_duplex_deep = fp.last_duplex_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
     fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
@@ -3579,16 +3583,27 @@ struct Batch {
     const uint64_t n_rows = lastr[0] + lastr[1];
     if (n_rows > (uint64_t)n_rec) throw std::runtime_error("device pipeline: " + std::to_string(n_rows) + " rows for the deep duplex kernels, more than the batch has records");
     fp.d_deep_rows.reserve((size_t)n_rows * sizeof(DeepRow) + 64); fp.d_deep_fams.reserve((size_t)n_list * sizeof(DuplexDeepMol) + 64);
-    hip_check(hipMemsetAsync(cnt(MISC_N_DEEP), 0, 4, s), "memset");
+    hip_check(hipMemsetAsync(cnt(MISC_N_DEEP), 0, 8, s), "memset");   // (both halves of the word: decided molecules, of which capped)
     DuplexDeepParams DP;
     DP.list = list; DP.n_list = n_list; DP.row0 = fp.d_deep_row0.as<uint64_t>();
     DP.rows = fp.d_deep_rows.as<DeepRow>(); DP.mols = fp.d_deep_fams.as<DuplexDeepMol>(); DP.n_done = cnt(MISC_N_DEEP);
+    DP.rows_walk = nullptr;
+    if (dup_deep_cap) {   // the scoring rows of capped sets in walk order: a set's copies lie where its rows lie, so the array is as long as `rows` — only a caller with a cap pays for it
+      fp.d_deep_walk.reserve((size_t)n_rows * sizeof(DeepRow) + 64);
+      DP.rows_walk = fp.d_deep_walk.as<DeepRow>();
+    }
     FastParams PD = P;
     PD.group_list = nullptr;
     // (both builds over the whole list: a workgroup whose molecule is the other build's returns at once)
-    FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
-    FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
-    FGX_LAUNCH(k_duplex_deep_cols, dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
+    if (dup_deep_cap) {
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128, 1>), dim3(n_list), dim3(128), 0, s, PD, DP);
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_cols<1>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
+    } else {
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_cols<0>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
+    }
     dup_deep_ran = true;   // (the count of decided molecules comes back with the batch's counters)
   }
 
@@ -3907,7 +3922,7 @@ struct Batch {
     for (int i = 0; i < FGX_STATS_LEN; i++) res->stats[i] = h_misc[MISC_STATS + i];
     res->n_deferred = (uint32_t)(h_misc[MISC_N_DEFERRED] & 0xFFFFFFFFull);
     fp.last_meth_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] & 0xFFFFFFFFull);
-    if (dup_deep_ran) fp.last_duplex_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull);
+    if (dup_deep_ran) { fp.last_duplex_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_duplex_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
     res->d_deferred = fp.d_deferred.as<uint32_t>();
     res->d_out_off = fp.d_offsets.as<uint64_t>();
     res->d_slot_size = fp.d_sizes.as<uint64_t>();

@@ -477,6 +477,9 @@ const char* fgx_pipeline_last_error(void);
  * (fgumi_amd/csrc/duplex_deep.inc: k_duplex_deep_parse + k_duplex_deep_cols) decided — up to 512 records, at most 255 retained reads per record
  * side; FGX_DUPLEX_DEEP=0 turns the path off and such molecules are deferred to the general path.  0 for a caller that has run no device batch. */
 uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c);
+/* ... and how many of those molecules a --max-reads-per-strand bit: decided by the CAP builds of the two kernels, which a caller with a cap > 0
+ * launches under FGX_DUPLEX_DEEP_CAP=1 (default off: such a molecule is deferred).  Always <= fgx_debug_last_duplex_deep. */
+uint32_t fgx_debug_last_duplex_deep_capped(const fgx_caller* c);
 
 /* Sizes for a parameter set: total blob bytes (records WITH block_size prefixes) and record count. */
 int fgx_sim_sizes(const fgx_sim_params* p, uint64_t* blob_len, uint64_t* n_rec);

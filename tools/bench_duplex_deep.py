@@ -17,7 +17,13 @@ The batch: --molecules (200 000) duplex molecules of 2 .. 100 pairs x 150 bp (`f
 Every library runs in a child interpreter of its own (FGX_LIB selects it at import).  A leg that did not run — no --parent-lib, no GPU — is listed under
 "missing".  --static FILE adds the kernels' static figures (a JSON object, see profiles/README.md) to the file.
 
-  python tools/bench_duplex_deep.py --parent-lib <parent commit's libfgumi_amd.so> [--legs a,b,c,d] [--out profiles/duplex_deep_bench.json]"""
+--max-reads-per-strand N: every caller of every leg gets the cap, the device legs of THIS library run under FGX_DUPLEX_DEEP_CAP=1 (the CAP builds of the two
+kernels; off by default), their lines carry fgx_debug_last_duplex_deep_capped, and the result goes to profiles/duplex_deep_cap_bench.json.  Leg (a) then
+first checks a sample (--check-molecules, 300) of the batch's kind byte for byte against the oracle (tests/orc.py), with nothing deferred.  The parent has
+one way only for a capped deep molecule — its device entry defers it, its host entry decides it: leg (c) is that way, leg (e) the parent's device entry alone
+on the whole batch (how many molecules it defers).
+
+  python tools/bench_duplex_deep.py --parent-lib <parent commit's libfgumi_amd.so> [--legs a,b,c,d,e] [--max-reads-per-strand N] [--out profiles/duplex_deep_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -32,25 +38,40 @@ SIM = dict(family_size=2, family_size_max=100, duplex=1)
 
 
 # ---- workers: one library each (the parent process set FGX_LIB / FGX_DUPLEX_DEEP) ----------------------------------------------------------------
-def _caller():
+def _caller(a):
     from fgumi_amd import DuplexConsensusCaller
-    return DuplexConsensusCaller("", "A", [1, 1, 0], cell_tag="CB", overlapping_consensus=True)
+    return DuplexConsensusCaller("", "A", [1, 1, 0], cell_tag="CB", overlapping_consensus=True, max_reads_per_strand=a.max_reads_per_strand)
 
 
-def _last_duplex_deep(c):
+def _last_duplex_deep(c, name="fgx_debug_last_duplex_deep"):
     from fgumi_amd import lib
-    if not hasattr(lib, "fgx_debug_last_duplex_deep"):
+    if not hasattr(lib, name):
         return None
-    lib.fgx_debug_last_duplex_deep.restype = C.c_uint32
-    lib.fgx_debug_last_duplex_deep.argtypes = [C.c_void_p]
-    return int(lib.fgx_debug_last_duplex_deep(c._h))
+    getattr(lib, name).restype = C.c_uint32
+    getattr(lib, name).argtypes = [C.c_void_p]
+    return int(getattr(lib, name)(c._h))
+
+
+def _check_sample(a, c):
+    """The device entry on a sample of the batch's kind against the oracle: nothing deferred, the bytes and the count equal."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fgx_opts
+    import orc
+    from fgumi_amd import simulate_grouped_reads
+    g = simulate_grouped_reads(a.check_molecules, **SIM)
+    o = fgx_opts.defaults(kind=1, duplex_min_reads=(1, 1, 0), duplex_max_reads_per_strand=a.max_reads_per_strand)
+    want = orc.process(o, g.blob, g.rec_off, g.rec_len, g.grp_first, batch_groups=100)
+    out = c.process_batch_device(g.to_device())
+    ok = out.n_deferred == 0 and out.count == want["count"] and out.to_host() == want["data"]
+    return {"molecules": int(g.n_grp), "deferred_molecules": int(out.n_deferred), "consensus_records": int(out.count), "equal_to_the_oracle": bool(ok)}
 
 
 def worker_device(a):
     """This library's device entry on the whole batch, the switch as the environment has it."""
     import numpy as np
     import torch
-    c = _caller()
+    c = _caller(a)
+    check = _check_sample(a, c) if a.max_reads_per_strand is not None and a.check_molecules > 0 else None
     dg = c.simulate_on_device(a.molecules, **SIM)
     n = np.diff(dg.grp_first.cpu().numpy().astype(np.int64))
     out = None
@@ -64,7 +85,8 @@ def worker_device(a):
     dt = (time.perf_counter() - t0) / a.steps
     print(json.dumps({"molecules": int(dg.n_grp), "raw_reads": int(dg.n_rec), "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 3),
                       "raw_reads_per_s": round(int(dg.n_rec) / dt), "consensus_records": int(out.count), "deferred_molecules": int(out.n_deferred),
-                      "duplex_deep_molecules": _last_duplex_deep(c), "kernel_ms": round(float(c.last_timing["kernels"]), 3),
+                      "duplex_deep_molecules": _last_duplex_deep(c), "duplex_deep_capped_molecules": _last_duplex_deep(c, "fgx_debug_last_duplex_deep_capped"),
+                      "max_reads_per_strand": a.max_reads_per_strand, "check_sample": check, "kernel_ms": round(float(c.last_timing["kernels"]), 3),
                       "molecules_above_64_records": int((n > 64).sum()), "share_of_molecules_above_64_records": round(float((n > 64).mean()), 4),
                       "share_of_reads_above_64_records": round(float(n[n > 64].sum() / n.sum()), 4)}))
     c.close()
@@ -75,7 +97,7 @@ def worker_host_entry(a):
     import torch
     from fgumi_amd import simulate_grouped_reads
     gs = simulate_grouped_reads(a.parent_molecules, **SIM)
-    c = _caller()
+    c = _caller(a)
     c.process_batch(gs.subset(0, 1))                          # warm-up: allocations, table images
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -94,10 +116,13 @@ def _last_json(text):
     raise ValueError("no JSON line in the child's output:\n" + text[-2000:])
 
 
-def _child(cmd, lib=None, switch=None, timeout=1200):
+def _child(cmd, lib=None, switch=None, timeout=1200, cap_switch=False):
     e = dict(os.environ)
     e.pop("FGX_LIB", None)
     e.pop("FGX_DUPLEX_DEEP", None)
+    e.pop("FGX_DUPLEX_DEEP_CAP", None)
+    if cap_switch:
+        e["FGX_DUPLEX_DEEP_CAP"] = "1"
     if lib:
         e["FGX_LIB"] = lib
     if switch is not None:
@@ -110,15 +135,20 @@ def _child(cmd, lib=None, switch=None, timeout=1200):
 
 def _me(a, worker):
     return [sys.executable, os.path.abspath(__file__), "--worker", worker, "--molecules", str(a.molecules), "--parent-molecules", str(a.parent_molecules),
-            "--steps", str(a.steps), "--warmup", str(a.warmup)]
+            "--steps", str(a.steps), "--warmup", str(a.warmup), "--check-molecules", str(a.check_molecules)] + \
+           (["--max-reads-per-strand", str(a.max_reads_per_strand)] if a.max_reads_per_strand is not None else [])
 
 
-def leg_device(a, switch):
-    runs = [_last_json(_child(_me(a, "device"), switch=switch)) for _ in range(a.repeats)]
+def leg_device(a, switch, lib=None):
+    capped = a.max_reads_per_strand is not None
+    cmd = _me(a, "device") + (["--check-molecules", "0"] if lib else [])           # (the oracle check is of this library's legs)
+    runs = [_last_json(_child(cmd, lib=lib, switch=switch, cap_switch=capped and lib is None)) for _ in range(a.repeats)]
     rates = [r["raw_reads_per_s"] for r in runs]
-    return {"workload": f"{a.molecules} duplex molecules x 2 .. 100 pairs x 150 bp, device-resident; FGX_DUPLEX_DEEP {'unset' if switch is None else switch}",
+    what = f"; --max-reads-per-strand {a.max_reads_per_strand}, FGX_DUPLEX_DEEP_CAP {'1' if lib is None else 'unset'}" if capped else ""
+    return {"workload": f"{a.molecules} duplex molecules x 2 .. 100 pairs x 150 bp, device-resident; FGX_DUPLEX_DEEP {'unset' if switch is None else switch}{what}",
             "repeats": runs, "raw_reads_per_s": rates, "mean_raw_reads_per_s": round(sum(rates) / len(rates)),
-            "deferred_molecules": [r["deferred_molecules"] for r in runs], "duplex_deep_molecules": [r["duplex_deep_molecules"] for r in runs]}
+            "deferred_molecules": [r["deferred_molecules"] for r in runs], "duplex_deep_molecules": [r["duplex_deep_molecules"] for r in runs],
+            "duplex_deep_capped_molecules": [r["duplex_deep_capped_molecules"] for r in runs]}
 
 
 def leg_a(a):
@@ -136,6 +166,12 @@ def leg_c(a):
     rates = [r["raw_reads_per_s"] for r in runs]
     return {"workload": f"the parent library's host entry on the first {a.parent_molecules} molecules of the batch", "repeats": runs, "raw_reads_per_s": rates,
             "mean_raw_reads_per_s": round(sum(rates) / len(rates))}
+
+
+def leg_e(a):
+    out = leg_device(a, None, lib=a.parent_lib)
+    out["note"] = "the parent library's device entry: the rate is that of the molecules it decided; the deferred ones are still to be decided by its host entry (leg c)"
+    return out
 
 
 def leg_d(a):
@@ -162,9 +198,12 @@ def main():
     ap.add_argument("--bench-steps", type=int, default=10)
     ap.add_argument("--bench-warmup", type=int, default=2)
     ap.add_argument("--static", default=None, help="JSON file with the kernels' static figures, copied into the result")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "duplex_deep_bench.json"))
+    ap.add_argument("--max-reads-per-strand", type=int, default=None, help="the callers' cap; this library's device legs then run under FGX_DUPLEX_DEEP_CAP=1")
+    ap.add_argument("--check-molecules", type=int, default=300, help="under a cap: molecules of the sample leg (a) checks against the oracle first (0: none)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--worker", choices=["device", "host_entry"], default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "duplex_deep_bench.json" if a.max_reads_per_strand is None else "duplex_deep_cap_bench.json")
     if a.worker:
         return {"device": worker_device, "host_entry": worker_host_entry}[a.worker](a)
     res = json.load(open(a.out)) if os.path.exists(a.out) else {}
@@ -177,7 +216,8 @@ def main():
             json.dump(res, f, indent=1)
             f.write("\n")
     stopped = False
-    for leg, key, fn, needs_parent in (("a", "device_entry", leg_a, False), ("b", "switch_0", leg_b, False), ("c", "parent_host_entry", leg_c, True), ("d", "nothing_deep", leg_d, True)):
+    for leg, key, fn, needs_parent in (("a", "device_entry", leg_a, False), ("b", "switch_0", leg_b, False), ("c", "parent_host_entry", leg_c, True), ("d", "nothing_deep", leg_d, True),
+                                      ("e", "parent_device_entry", leg_e, True)):
         if leg not in a.legs.split(","):
             continue
         if stopped:                                         # an earlier leg's child failed or hung: nothing more is started on the device in this call
