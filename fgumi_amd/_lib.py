@@ -86,7 +86,7 @@ EXPORTS = ["fgx_options_default", "fgx_create", "fgx_destroy", "fgx_last_error",
            "fgx_filter_records", "fgx_filter_records_device", "fgx_filter_last_output_device",
            "fgx_record_boundaries_device", "fgx_inflate_block_host", "fgx_inflate_block_two_phase_host", "fgx_deflate_block_host", "fgx_run_bam", "fgx_run_bam_rejects", "fgx_bgzf_inflate_device_bench", "fgx_bgzf_deflate_device_bench", "fgx_bgzf_recompress_file", "fgx_pipeline_last_error",
            "fgx_set_reference", "fgx_methylation_annotate_host", "fgx_methylation_runs_host", "fgx_methylation_mm_ml_host", "fgx_canon_duplex_host", "fgx_canon_duplex_runs_host", "fgx_canon_simplex_host", "fgx_canon_codec_host", "fgx_simplex_rejects_host", "fgx_strand_rejects_host", "fgx_balanced_shards", "fgx_regenerate_alignment_tags_host",
-           "fgx_debug_last_duplex_deep", "fgx_debug_last_duplex_deep_capped"]
+           "fgx_debug_last_duplex_deep", "fgx_debug_last_duplex_deep_capped", "fgx_debug_last_boundary_rounds"]
 
 _lib = None
 
@@ -211,6 +211,9 @@ def load():
     if hasattr(L, "fgx_debug_last_duplex_deep_capped"):     # (likewise: a library built before the CAP builds of duplex_deep.inc)
         L.fgx_debug_last_duplex_deep_capped.argtypes = [VP]
         L.fgx_debug_last_duplex_deep_capped.restype = U32
+    if hasattr(L, "fgx_debug_last_boundary_rounds"):        # (likewise: a library built before this export)
+        L.fgx_debug_last_boundary_rounds.argtypes = [VP]
+        L.fgx_debug_last_boundary_rounds.restype = U32
     L.fgx_set_general_only.argtypes = [VP, I]
     L.fgx_set_general_only.restype = None
     L.fgx_set_fast_lds_bytes.argtypes = [VP, U32]

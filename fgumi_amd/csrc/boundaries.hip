@@ -105,9 +105,10 @@ __global__ void k_bound_walk(const uint8_t* __restrict__ s, uint64_t len, uint64
   uint32_t b = 0;
   for (;;) {
     if (p + 4 > len) { e = p | TERMINAL; break; }              // (also p == len: the data ends with a whole record)
-    if (p >= hi) { e = p; break; }
     const uint32_t bs = bld32(s + p);
-    if (p + 4 + (uint64_t)bs > len) { e = p | TERMINAL; break; }
+    if (p + 4 + (uint64_t)bs > len) { e = p | TERMINAL; break; }   // (before the segment's end is looked at: a cut-off record that begins a later
+                                                                  // segment is one no guess proposes — announced as a start it cost a repair round)
+    if (p >= hi) { e = p; break; }
     if (bs < 32) b = 1;                                        // not a BAM record (reported once the table is verified)
     n++;
     p += 4 + (uint64_t)bs;
@@ -165,6 +166,7 @@ int record_boundaries_device(fgx_caller* c, const uint8_t* d_stream, uint64_t le
                              uint64_t cap, uint64_t* n_rec, uint64_t* consumed) {
   hipStream_t s = c->stream;
   *n_rec = 0; *consumed = start;
+  c->last_boundary_rounds = 0;                                 // (also for a call that returns before the table is built: not the call before's)
   if (start >= len) return 0;
   const uint64_t n_seg = (len + SEG - 1) / SEG;
   if (n_seg > 0x7FFFFFFFull) { c->err = "fgx_record_boundaries_device: stream longer than 2^31 segments"; return 1; }

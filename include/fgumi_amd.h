@@ -480,6 +480,8 @@ uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c);
 /* ... and how many of those molecules a --max-reads-per-strand bit: decided by the CAP builds of the two kernels, which a caller with a cap > 0
  * launches under FGX_DUPLEX_DEEP_CAP=1 (default off: such a molecule is deferred).  Always <= fgx_debug_last_duplex_deep. */
 uint32_t fgx_debug_last_duplex_deep_capped(const fgx_caller* c);
+/* Repair rounds of the last fgx_record_boundaries_device call on `c` (0 = every segment's guess was right; fgx_run_bam sums them into boundary_repair_rounds). */
+uint32_t fgx_debug_last_boundary_rounds(const fgx_caller* c);
 
 /* Sizes for a parameter set: total blob bytes (records WITH block_size prefixes) and record count. */
 int fgx_sim_sizes(const fgx_sim_params* p, uint64_t* blob_len, uint64_t* n_rec);

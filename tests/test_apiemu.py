@@ -389,6 +389,20 @@ def test_grouping_kernels_on_hostile_streams_on_the_host():
     run_isolated("test_apiemu", "check_grouping_kernels_on_hostile_streams", env=env())
 
 
+def check_boundary_kernels_on_hostile_streams():
+    """tests/boundary_cases.py on boundaries.hip compiled for the host (its threads run one after the other, in segment order): segment-edge geometry,
+    decoy chains, far and terminal fake links, malformed links and records, the entry's contract, one caller over all of it in a shuffled order — every
+    stream flush against an inaccessible page, with nothing behind its last byte; offsets, lengths, `consumed` and the return code against each case's
+    constructed answer, and the repair rounds of every call (none without a decoy, at least one with, at least three for the far jump and the terminal
+    link).  (tests/test_gpu_boundaries.py runs the same checks on an MI355X.)"""
+    import boundary_cases
+    boundary_cases.check("all", "host")
+
+
+def test_boundary_kernels_on_hostile_streams_on_the_host():
+    run_isolated("test_apiemu", "check_boundary_kernels_on_hostile_streams", env=env())
+
+
 @pytest.mark.parametrize("resident", [0, 1])
 @pytest.mark.parametrize("defer", ["mod3", "indel"])
 def test_pipeline_resubmits_only_the_deferred_groups(defer, resident):
@@ -405,7 +419,7 @@ def test_pipeline_resubmits_only_the_deferred_groups(defer, resident):
                         "-p", "no:cacheprovider"], env=e, cwd=apiemu.ROOT, capture_output=True, text=True, timeout=1800)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     trace = p.stdout + p.stderr
-    assert "12 passed" in trace
+    assert "13 passed" in trace
     assert trace.count("decided alone") > (20 if defer == "mod3" else 0) and "the whole batch through the host entry" not in trace
 
 

@@ -244,6 +244,33 @@ def test_chunks_that_keep_no_record_at_all(tmp_path):
     c.close()
 
 
+def test_record_like_payloads_between_the_families_cost_repair_rounds_only(tmp_path):
+    """FindBoundaries inside fgx_run_bam — behind the BAM header (a start other than 0), on the chunk's 256-aligned base, with the leftover of chunk after
+    chunk in front: after every seventh record an untagged carrier whose B:C array is a chain of three fake records.  Where a segment's guess meets such a
+    chain first, the mutual check of the walks repairs it (boundary_repair_rounds says that it had to); the grouper drops the carriers, and the consensus
+    BAM is the oracle's over the families alone."""
+    refs = [("chr1", 1000000)]
+    src, dst = str(tmp_path / "in.bam"), str(tmp_path / "out.bam")
+    g = simulate_grouped_reads(400, family_size=3)
+    recs = [bytes(g.blob[int(o) - 4:int(o) + int(l)]) for o, l in zip(g.rec_off, g.rec_len)]
+    fake = bamutil.make_record("fake", "ACGT" * 10, [30] * 40, flag=0x4, ref_id=-1, pos=-1)
+    fake = len(fake).to_bytes(4, "little") + fake
+    carrier = bamutil.make_record("untagged", "ACGT" * 10, [30] * 40, flag=0, ref_id=0, pos=5, tags=[("zz", "raw", b"BC" + (3 * len(fake)).to_bytes(4, "little") + fake * 3)])
+    carrier = len(carrier).to_bytes(4, "little") + carrier
+    mixed = b"".join(r + (carrier if i % 7 == 6 else b"") for i, r in enumerate(recs))
+    bgzf.write_bam(src, bgzf.grouped_input_header(refs), refs, mixed)
+    c = _caller()
+    st = c.run_bam(src, dst, chunk_raw_bytes=1 << 16)
+    want = orc.process(fgx_opts.defaults(min_reads=1), g.blob, g.rec_off, g.rec_len, g.grp_first)
+    text, orefs, stream, off, ln = bgzf.read_bam(dst)
+    got = b"".join(bytes(stream[int(o) - 4:int(o) + int(l)]) for o, l in zip(off, ln))
+    c.close()
+    assert st["chunks"] > 1
+    assert got == want["data"] and st["consensus_records"] == want["count"] == len(off)
+    assert st["kept_records"] == g.n_rec
+    assert st["boundary_repair_rounds"] >= 1, st["boundary_repair_rounds"]
+
+
 def _rejects_case(tmp_path, caller, opts, g, batch_groups, chunk, **run_kw):
     """fgx_run_bam_rejects: consensus BAM == the oracle's records, rejects BAM == the oracle's rejects (batch-input order) under the INPUT header."""
     refs = [("chr%d" % (i + 1), 2147483647) for i in range(24)]
