@@ -1534,6 +1534,13 @@ void fgx_debug_last_packed_rows(const fgx_caller* c, uint64_t* out2) {
   out2[0] = out2[1] = 0;
   if (c && c->fast) { out2[0] = c->fast->fp.last_packed_clean; out2[1] = c->fast->fp.last_packed_general; }
 }
+// the packed build's families with overlapping mates in the last device batch by the step that corrected them: out3[0] the packed step (eight
+// shared bases per lane), out3[1] the byte-wise steps (FGX_S2_PACKED_OVERLAP=0: all of them), out3[2] those of out3[1] that a shared quality of
+// 128 or more voted out of the packed step
+void fgx_debug_last_packed_overlap(const fgx_caller* c, uint64_t* out3) {
+  if (!out3) return;
+  for (int i = 0; i < 3; i++) out3[i] = (c && c->fast) ? c->fast->fp.last_packed_overlap[i] : 0;
+}
 // k_call_full's answers in the last device batch (fastpath.h, FullResult): out4[0] column answers that went to the pair writer through the result array,
 // [1] column answers scattered into the scratch planes, [2] families whose answers the pair writer applies (families without items included), [3] families
 // the pair writer takes but whose items a list's end cuts in two: not in one piece (their answers are scattered)

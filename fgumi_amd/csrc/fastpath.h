@@ -116,7 +116,9 @@ constexpr uint32_t FULL_RESULT_MAX_ITEMS = 64;   // a lane of the writer's wavef
 #endif
 // counters of the path (fgx_debug_last_full_results), spread over STAT_SLOTS slots of FULL_STATS_STRIDE words: [0] column answers through the array, [1] column answers
 // scattered, [2] families the writer applies, [3] families refused because their items are not in one piece, [4] families refused because they hold more than 64 items
-constexpr int FULL_STATS_N = 5, FULL_STATS_STRIDE = 8;
+// ([5 .. 8) of a slot: k_split_finish's counters of the packed overlap step — packed, byte-wise, of those voted out by the guard)
+constexpr int FULL_STATS_N = 5, FULL_STATS_STRIDE = 8, OV_STATS_N = 3;
+static_assert(FULL_STATS_N + OV_STATS_N <= FULL_STATS_STRIDE, "the overlap counters share the slots of the result counters");
 // the family's word in its fragment EndDesc: first slot | items << 32 | (in one piece) << 48
 FP_HD uint64_t full_range_word(uint32_t first, uint32_t items, bool whole) {
   return (uint64_t)first | ((uint64_t)(items < 0xFFFFu ? items : 0xFFFFu) << 32) | ((uint64_t)(whole ? 1u : 0u) << 48);
@@ -174,10 +176,13 @@ struct SplitOut {           // 32 bytes: what k_split_cols decided for a family;
   uint8_t n;                // records of the family
   uint16_t lc_a, lc_b;      // consensus lengths
   uint32_t rej;             // rejected reads: insufficient | zero length << 8 | orphan << 16
-  uint32_t ov_agree, ov_dis, ov_corr;   // overlapping-bases counters
-  uint32_t depth_stats;     // direct records: max | min << 8 of the per-base depths of end A, the same of end B << 16 (the cD / cM tags; at most 16 reads per end)
+  uint32_t ov_agree, ov_dis, ov_corr;   // overlapping-bases counters (ov_corr: the count in S2_OV_COUNT, above it which step corrected a packed-build family)
+  uint32_t depth_stats;    // direct records: max | min << 8 of the per-base depths of end A, the same of end B << 16 (the cD / cM tags; at most 16 reads per end)
 };
 static_assert(sizeof(SplitRec) == 32 && sizeof(SplitFam) == 32 && sizeof(SplitOut) == 32, "split descriptors are moved as two 16-byte pieces");
+// SplitOut.ov_corr of a family the packed build finished (fgx_debug_last_packed_overlap): the overlap of its mates was corrected by the packed
+// step (eight bases per lane) / by the byte-wise steps / by those because a shared quality of 128 or more voted it out of the packed step
+constexpr uint32_t S2_OV_COUNT = 0x0FFFFFFFu, S2_OV_PACKED = 1u << 28, S2_OV_BYTEWISE = 1u << 29, S2_OV_GUARD = 1u << 30;
 
 // ---- direct records (round 4): k_split_cols writes the consensus records of its families itself ------------------------------------
 // k_split_parse predicts the exact bytes of every family's records (final lengths at the reads' 3' ends, consensus lengths, tag
@@ -227,7 +232,7 @@ struct FastParams {
   uint32_t lds_tile_bytes;
   uint32_t lds_wave_bytes;
   uint32_t s2_partner;             // k_split_cols<.., 1>: a <.., 2> launch over the same families follows (else it hands the families that are not its shape to the next launch)
-  uint32_t s2_packed;              // k_split_cols: 1 = ends of at least s2_nsafe rows try the packed pass first (round 5; FGX_S2_PACKED=0: measurements); | 2: debug counters; | 4: the clean test (FGX_S2_CLEAN_ROWS=0: off)
+  uint32_t s2_packed;              // k_split_cols: 1 = ends of at least s2_nsafe rows try the packed pass first (round 5; FGX_S2_PACKED=0: measurements); | 2: debug counters; | 4: the clean test (FGX_S2_CLEAN_ROWS=0: off); | 8: the packed overlap step (FGX_S2_PACKED_OVERLAP=0: off)
   uint32_t s2_nsafe;               // k_split_cols: unanimous_cap_depth(tables, min_input_bq) — agreeing observations from which a column is the cap for certain (gate_core.h)
   FullItem* full_items; uint32_t* full_count; uint32_t full_cap;   // N_LISTS append lists of `full_cap` items each
   uint32_t full_results;           // 1: k_call_full's answers go to the pair writer through a result array (FullResult above; FGX_FULL_RESULTS=0: off)
@@ -320,7 +325,8 @@ struct FastPath {
   uint32_t last_meth_clipped = 0;          // ... of which held a record of more than one CIGAR op (clips around one aligned block) and were not deferred
   uint32_t last_routed = 0;                // families the split pipeline handed to the k_simplex_wave2 chain in the last batch
   uint64_t last_packed_clean = 0, last_packed_general = 0;        // ... of the packed build's: by its clean row loop (no quality read) / by its general one
-  uint64_t last_packed_families = 0, last_classic_families = 0;   // families of the last batch finished by k_split_cols's packed build / by its classic builds (k_split_finish counts them)
+  uint64_t last_packed_overlap[OV_STATS_N] = {0, 0, 0};           // ... whose overlapping mates the packed step corrected / the byte-wise steps / of those: voted out of the packed step by its guard
+  uint64_t last_packed_families = 0, last_classic_families = 0;  // families of the last batch finished by k_split_cols's packed build / by its classic builds (k_split_finish counts them)
   uint32_t last_split_build = 0;           // first-stage build of the last batch: 0 classic alone (or no split pipeline), 1 packed alone, 2 packed + partner launch
   uint32_t last_first_stage_retries = 0;   // families the first stage handed to the next launch
   uint32_t last_launches = 0, last_host_syncs = 0;   // kernel launches (library scans not counted) / host synchronisations of the last batch

@@ -2896,7 +2896,7 @@ __global__ void k_col_bound(const uint32_t* __restrict__ grp_first, const uint32
 
 __global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, unsigned long long* __restrict__ out, const unsigned long long* __restrict__ full_stats, uint32_t full_out) {
   uint32_t k = threadIdx.x;   // one thread per counter; the slots' entries 28 .. 31 are diagnostics (k_split_finish: families per build) and go to out[40 ..]
-  if (k >= 32 && k < 32 + FULL_STATS_N) {    // the counters of the result array (fastpath.h, FullResult): slots of their own
+  if (k >= 32 && k < 32 + FULL_STATS_N + OV_STATS_N) {    // the counters of the result array (fastpath.h, FullResult) and, behind them, of the packed overlap step: slots of their own
     unsigned long long v = 0;
     for (int i = 0; i < STAT_SLOTS; i++) v += full_stats[(size_t)i * FULL_STATS_STRIDE + (k - 32)];
     out[full_out + (k - 32)] = v;
@@ -2950,13 +2950,15 @@ enum MiscWord : uint32_t {
   MISC_BUILD_FAMILIES = 40,  // [40, 44): the slots' diagnostics (k_reduce_stats): families finished by k_split_cols's packed build, by its classic builds, by the packed build's clean / general row loop
   MISC_N_SLOW = 44,          // duplex / CODEC: records the fast writer leaves to the per-field kernel
   MISC_FULL_RESULTS = 46,    // [46, 51): items answered through the result array, items scattered, families the writer applies, families refused as not in one piece, families refused for more than 64 items
-  MISC_READ_BACK = 51,       // words the end of a batch copies to the host
-  MISC_WORDS = 52
+  MISC_PACKED_OVERLAP = 51,  // [51, 54): behind them in the same slots — packed-build families whose overlapping mates the packed step corrected, the byte-wise steps, of those voted out by the guard
+  MISC_READ_BACK = 54,       // words the end of a batch copies to the host
+  MISC_WORDS = 56
 };
 constexpr uint32_t MISC_SPLIT_WINDOW = MISC_N_BIG - MISC_N_RETRY + 1;   // retry, route and big counts of a split stage come back as ONE copy
 static_assert(FGX_STATS_LEN <= MISC_COLS_USED && MISC_BUILD_FAMILIES == 40 && MISC_BUILD_FAMILIES + (32 - FGX_STATS_LEN) <= MISC_N_SLOW,
               "k_reduce_stats writes words [0, FGX_STATS_LEN) and 40 .. of misc");
 static_assert(MISC_N_METH_CLIPPED == MISC_N_DEFERRED + 1 && MISC_N_METH_CLIPPED < MISC_READ_BACK, "meth_clipped_counter: the word behind the deferred count");
+static_assert(MISC_PACKED_OVERLAP == MISC_FULL_RESULTS + FULL_STATS_N && MISC_PACKED_OVERLAP + OV_STATS_N <= MISC_READ_BACK, "k_reduce_stats writes the overlap counters behind the result counters");
 static_assert(MISC_N_RETRY < MISC_N_ROUTE && MISC_N_ROUTE < MISC_N_BIG && MISC_SPLIT_WINDOW == 7 && MISC_N_SLOW < MISC_READ_BACK && MISC_READ_BACK <= MISC_WORDS, "misc layout");
 
 // ---- environment switches ---------------------------------------------------------------------------------------------------------------
@@ -2976,6 +2978,7 @@ struct ProcessSwitches {   // read once per process, at the first batch
   const int nosum = env_int(fgx_knob("FGX_S2_NOSUM"), 1);                // 0: every end through the f32 sums
   const int packed = env_int(getenv("FGX_S2_PACKED"), 1);                // 0: the 64-column passes only
   const bool clean_rows = env_not0(getenv("FGX_S2_CLEAN_ROWS"));         // 0: the packed pass reads the qualities of every family (no clean test)
+  const bool packed_overlap = env_not0(getenv("FGX_S2_PACKED_OVERLAP")); // 0: the overlap of every family is corrected byte by byte (no packed step)
   const bool full_results = FGX_FULL_RESULTS_DEFAULT ? env_not0(getenv("FGX_FULL_RESULTS")) : env_is1(getenv("FGX_FULL_RESULTS"));   // k_call_full's answers through the result array (fastpath.h, FullResult)
   const int s2_debug = env_int(fgx_knob("FGX_S2_DEBUG"), 0);
   const int pace = env_int(fgx_knob("FGX_S2_PACE"), 1);                  // 0: all record kernels up front
@@ -3147,7 +3150,7 @@ struct Batch {
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
     if (!fp.canon_second_pass) fp.last_duplex_deep = fp.last_duplex_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
-    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
+    fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_packed_overlap) v = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
     fp.d_offsets.reserve(((size_t)n_slots + 1) * 8);
@@ -3234,7 +3237,7 @@ struct Batch {
     P.min_reads = o.min_reads; P.max_reads = o.max_reads;
     P.min_input_bq = o.min_input_base_quality; P.min_cons_bq = o.min_consensus_base_quality;
     // k_split_cols's sum-free observation step: from how many agreeing observations a column is the cap whatever their qualities (gate_core.h)
-    P.s2_packed = (ps.packed ? 1u : 0u) | ((ps.packed && ps.s2_debug) ? 2u : 0u) | ((ps.packed && ps.clean_rows) ? 4u : 0u);
+    P.s2_packed = (ps.packed ? 1u : 0u) | ((ps.packed && ps.s2_debug) ? 2u : 0u) | ((ps.packed && ps.clean_rows) ? 4u : 0u) | ((ps.packed && ps.packed_overlap) ? 8u : 0u);
     P.s2_nsafe = ps.nosum ? unanimous_cap_depth(c->h_tables.t, (uint32_t)o.min_input_base_quality & 0xFFu, 64u) : FGX_NEVER_CAP;
     P.trim = o.trim; P.overlap = o.overlapping_consensus;
     if (duplex) {   // single-strand caller of the duplex caller (duplex_caller.rs:474-489): min_reads 1, min consensus base quality 2
@@ -3931,6 +3934,7 @@ struct Batch {
     fp.last_packed_families = h_misc[MISC_BUILD_FAMILIES]; fp.last_classic_families = h_misc[MISC_BUILD_FAMILIES + 1];
     fp.last_packed_clean = h_misc[MISC_BUILD_FAMILIES + 2]; fp.last_packed_general = h_misc[MISC_BUILD_FAMILIES + 3];
     for (int i = 0; i < FULL_STATS_N; i++) fp.last_full_results[i] = h_misc[MISC_FULL_RESULTS + i];
+    for (int i = 0; i < OV_STATS_N; i++) fp.last_packed_overlap[i] = h_misc[MISC_PACKED_OVERLAP + i];
     res->cols_used = h_misc[MISC_COLS_USED];
     res->full_items = n_full;
   }

@@ -169,6 +169,124 @@ FGX_HD void finalize(const Acc& a, bool inl, bool lrev, uint32_t lenE, uint32_t 
   }
 }
 
+// ---- the overlap correction of two mates on packed words (round 8; simplex_split.inc phase 2; overlapping.rs:236-336) ---------------------
+// A lane takes one pair and EIGHT neighbouring shared positions.  The groups are aligned to the mate whose first shared base is its base 0
+// ("A": one of the two offsets of a pair is always 0): A's qualities are two whole dwords, its codes one whole word, and they belong to the
+// lane alone.  The other mate ("B") starts `off` positions into its read: its bytes are gathered from the neighbouring aligned words with a
+// funnel shift (ov_gather_q / ov_gather_c) and what changes goes back as XOR deltas (ov_scatter_q / ov_scatter_c) — a word of B is shared by
+// two neighbouring groups, their positions in it are disjoint, so the deltas compose in any order, and a lane that loads a word after a
+// neighbour's delta finds its own positions as they were.
+//
+// The rule per shared position (c1, c2 the codes, qa, qb the qualities; symmetric in the mates): nothing if either code is 15; c1 == c2: both
+// qualities min(qa + qb, 93); else both qualities max(|qa - qb|, 2) and both codes the one of the higher quality (15 on a tie); a new quality
+// below the floor clears both codes (`drop`, also on agreement: the clean rows above rest on it).  Both mates end with ONE quality and ONE code.
+// Byte-wise sums are exact while qa + qb < 256: the kernel sends a family with a shared quality of 128 or more down its byte-wise path
+// (ov_high is the test); the arithmetic below masks bit 7 away so that such a byte OUTSIDE the overlap cannot carry into a neighbour.
+FGX_HD uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t n) {  // v_alignbyte_b32: ({hi, lo} >> 8 n), low word; n = 0 .. 3
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_alignbyte(hi, lo, n);
+#else
+  return (uint32_t)(((((unsigned long long)hi) << 32) | lo) >> (8u * (n & 3u)));
+#endif
+}
+FGX_HD uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t n) {   // v_alignbit_b32: ({hi, lo} >> n), low word; n = 0 .. 31
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_alignbit(hi, lo, n);
+#else
+  return (uint32_t)(((((unsigned long long)hi) << 32) | lo) >> (n & 31u));
+#endif
+}
+FGX_HD uint32_t popc(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_popcount(x);
+#else
+  x = x - ((x >> 1) & 0x55555555u); x = (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
+  return (((x + (x >> 4)) & 0x0F0F0F0Fu) * 0x01010101u) >> 24;
+#endif
+}
+FGX_HD uint32_t widen(uint32_t h) { return h - (h >> 7); }   // bit 7 of each byte -> 0x7F (h holds bits 7 only): a select mask for bytes below 128 — every quality the step computes, every code
+FGX_HD uint32_t swap_nibbles(uint32_t x) { return ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu); }   // BAM order (even position high) <-> position order
+// the four codes of half h of a word, a byte each: from BAM order / from position order
+FGX_HD uint32_t expand_bam(uint32_t c, int h) { const uint32_t P = perm(c, c, h ? 0x03030202u : 0x01010000u); return ((P >> 4) & 0x000F000Fu) | (P & 0x0F000F00u); }
+FGX_HD uint32_t expand_pos(uint32_t c, int h) { const uint32_t P = perm(c, c, h ? 0x03030202u : 0x01010000u); return (P & 0x000F000Fu) | ((P >> 4) & 0x0F000F00u); }
+// ... and back: eight bytes of at most 15 to one word
+FGX_HD uint32_t compress_bam(uint32_t lo, uint32_t hi) { return perm((hi << 4) | (hi >> 8), (lo << 4) | (lo >> 8), 0x06040200u); }
+FGX_HD uint32_t compress_pos(uint32_t lo, uint32_t hi) { return perm(hi | (hi >> 4), lo | (lo >> 4), 0x06040200u); }
+
+// positions of group k inside the overlap [0, cn): 0xFF per byte (k < ceil(cn / 8); a lane outside the index space passes cn = 0)
+FGX_HD void ov_in_masks(uint32_t cn, uint32_t k, uint32_t* ml, uint32_t* mh) {
+  const uint32_t nv = cn > 8u * k ? cn - 8u * k : 0u;
+  const unsigned long long m = nv >= 8u ? ~0ull : (1ull << (8u * nv)) - 1ull;
+  *ml = (uint32_t)m; *mh = (uint32_t)(m >> 32);
+}
+// B's eight qualities from the three aligned dwords that hold bytes [4 (off / 4) + 8 k, + 12) of its row; s = off & 3
+FGX_HD void ov_gather_q(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t s, uint32_t* qx, uint32_t* qy) { *qx = alignbyte(d1, d0, s); *qy = alignbyte(d2, d1, s); }
+// B's eight codes in POSITION order from the two aligned words that hold positions [8 (off / 8) + 8 k, + 16); sn = off & 7
+FGX_HD uint32_t ov_gather_c(uint32_t w0, uint32_t w1, uint32_t sn) { return alignbit(swap_nibbles(w1), swap_nibbles(w0), 4u * sn); }
+// the deltas of B on their way back: the dwords of ov_gather_q / the words of ov_gather_c (BAM order again)
+FGX_HD void ov_scatter_q(uint32_t dx, uint32_t dy, uint32_t s, uint32_t* e /* [3] */) {
+  const unsigned long long D = (((unsigned long long)dy) << 32) | dx, L = D << (8u * s);
+  e[0] = (uint32_t)L; e[1] = (uint32_t)(L >> 32); e[2] = (uint32_t)((D >> 8) >> (56u - 8u * s));    // (s = 0: shifted out)
+}
+FGX_HD void ov_scatter_c(uint32_t d, uint32_t sn, uint32_t* f /* [2] */) {
+  f[0] = swap_nibbles(d << (4u * sn)); f[1] = swap_nibbles((d >> 4) >> (28u - 4u * sn));
+}
+// a quality of 128 or more at a shared position: the family is the byte-wise step's
+FGX_HD bool ov_high(uint32_t qax, uint32_t qay, uint32_t qbx, uint32_t qby, uint32_t ml, uint32_t mh) { return ((((qax | qbx) & ml) | ((qay | qby) & mh)) & H) != 0u; }
+
+// four positions: qa, qb the qualities, ca, cb the codes as bytes, inr = ov_in_masks, mb4 = 4 x the floor (at most 128).  Bit 7 of a byte of
+// agree / dis / chg: a valid agreement / a valid disagreement / an agreement whose sum differs from qa or qb.
+struct OvHalf { uint32_t newq, newc, validM, agree, dis, chg; };
+FGX_HD void ov_half(uint32_t qa, uint32_t qb, uint32_t ca, uint32_t cb, uint32_t inr, uint32_t mb4, OvHalf& o) {
+  const uint32_t L = 0x7F7F7F7Fu;
+  qa &= L; qb &= L;
+  const uint32_t isN = ((ca + 0x71717171u) | (cb + 0x71717171u)) & H;          // a code is 15 (codes are at most 15: no carry)
+  const uint32_t ne = ((ca ^ cb) + L) & H;
+  const uint32_t valid = inr & ~isN & H;
+  const uint32_t s = qa + qb;                                                  // (both below 128: no carry)
+  const uint32_t overM = widen((s | ((s & L) + 0x22222222u)) & H);             // 94 and more: bit 7 of s, or of (s & 127) + 34
+  const uint32_t nq = ((s & L) & ~overM) | (0x5D5D5D5Du & overM);                // (a sum below 94 has no bit 7)
+  const uint32_t xg = (qa | H) - qb, yg = (qb | H) - qa;                       // bit 7: qa >= qb / qb >= qa; below it the difference mod 128 (no borrow)
+  const uint32_t ageM = widen(xg & H);
+  const uint32_t ad = ((xg & ageM) | (yg & ~ageM)) & L;
+  const uint32_t lt2M = widen(~((ad | H) - 0x02020202u) & H);
+  const uint32_t dq = (ad & ~lt2M) | (0x02020202u & lt2M);
+  const uint32_t neM = widen(ne);
+  o.newq = (dq & neM) | (nq & ~neM);
+  const uint32_t dropM = widen(~((o.newq | H) - mb4) & H);                     // the new quality (at most 93) is below the floor
+  o.newc = (((ca & ageM) | (cb & ~ageM)) | (0x0F0F0F0Fu & widen(xg & yg & ne))) & ~dropM;   // (an agreement: ca == cb; a tie: N)
+  o.validM = widen(valid);                                                     // (a valid position's qualities are below 128 on both mates: ov_high)
+  o.agree = valid & ~ne; o.dis = valid & ne;
+  o.chg = o.agree & (((nq ^ qa) | (nq ^ qb)) + L);
+}
+// One lane's step.  In: A's qualities and code word (BAM order) as loaded, B's as gathered, the masks, the floor.  Out: A's words to store, B's
+// deltas (qualities: bytes in A's alignment; codes: position order) and the counts — agreements | disagreements << 16, changed agreements.
+// The two halves ONE AFTER THE OTHER (the empty asm makes the second wait for the first): interleaved, as the scheduler would have them, their
+// temporaries take the kernel past 64 vector registers — eight wavefronts per SIMD — and into scratch.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FGX_PK_THEN(a, b, c, d, e, f, g, h, i, j) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "+v"(i), "+v"(j))
+#else
+#define FGX_PK_THEN(a, b, c, d, e, f, g, h, i, j) ((void)0)
+#endif
+struct OvStep { uint32_t qa[2], ca, dq[2], dc, n_ad, n_chg; };
+FGX_HD void ov_step(uint32_t qax, uint32_t qay, uint32_t caw, uint32_t qbx, uint32_t qby, uint32_t cbp, uint32_t ml, uint32_t mh, uint32_t mb4, OvStep& o) {
+  uint32_t a8[2], d8[2];                                                       // A's new codes and B's code deltas, a byte each
+  o.n_ad = 0; o.n_chg = 0;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const uint32_t qa = h ? qay : qax, qb = h ? qby : qbx, ca = expand_bam(caw, h), cb = expand_pos(cbp, h);
+    OvHalf r;
+    ov_half(qa, qb, ca, cb, h ? mh : ml, mb4, r);
+    o.qa[h] = (r.newq & r.validM) | (qa & ~r.validM);
+    a8[h] = (r.newc & r.validM) | (ca & ~r.validM);
+    o.dq[h] = (r.newq ^ qb) & r.validM;
+    d8[h] = (r.newc ^ cb) & r.validM;
+    o.n_ad += popc(r.agree) + (popc(r.dis) << 16); o.n_chg += popc(r.chg);
+    if (h == 0) FGX_PK_THEN(o.qa[0], a8[0], o.dq[0], d8[0], o.n_ad, o.n_chg, qay, qby, caw, cbp);
+  }
+  o.ca = compress_bam(a8[0], a8[1]); o.dc = compress_pos(d8[0], d8[1]);
+}
+
 // One observation of base b and quality q: ConsensusBaseBuilder::add from zero leaves s[b] = correct[q], s[other] = error_per_alt[q]
 // exactly (Kahan's first step adds to 0), and the call (try_unanimous_fast_path, else call_full: base_builder.rs:883-1081) is a function
 // of q alone — evaluated here by the very functions k_call_full runs (column_call, consensus_math.h), once per caller.  t1[q] = the

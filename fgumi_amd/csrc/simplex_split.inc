@@ -818,7 +818,7 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
   }
 
   // ---- 2. overlapping-bases pre-correction in LDS (overlapping.rs:236-336, 627-684) -------------------------------------------
-  uint32_t ov_agree = 0, ov_dis = 0, ov_corr = 0;             // (wave-uniform: counted with ballots)
+  uint32_t ov_agree = 0, ov_dis = 0, ov_corr = 0;             // (wave-uniform: counted with ballots byte by byte, summed over the wavefront once by the packed step)
   {
     // one shared base of a pair: o1 / o2 = sequence bytes, sh1 / sh2 = nibble shifts, q1 / q2 = quality bytes of the two reads.
     // Agreement: both qualities become min(qa + qb, 93).  Disagreement: the higher quality's base wins with the difference (at
@@ -856,7 +856,77 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
     if (om) {
       const uint32_t np = (uint32_t)__popcll(om), fp = (uint32_t)__builtin_ctzll(om);
       const uint32_t cn0 = rlane(ov_cnt, fp);
-      if (ov_uniform && np > 1u && cn0 < 64u) {
+      bool ov_packed = false, ov_guard = false;
+      if constexpr (COLS == 1) {
+        // ---- 2a. (round 8) EIGHT shared bases per lane on packed words (packed_core.h, ov_step): pairs x groups of eight as one index space, 64
+        //      per step — 8 pairs x 40 bases in one step, 8 x 150 in three.  For families of one geometry and two or more overlapping pairs (one
+        //      pair of a few bases is cheaper byte by byte).  The groups are aligned to the mate whose offset is 0 (one of the two always is: the
+        //      overlap starts at the later of the two starts) — its words are the lane's own and are stored as they are; the other mate's words
+        //      are shared with the neighbouring group and get XOR deltas of the lane's own positions (LDS atomics: they compose in any order, and
+        //      a lane that loads after a neighbour's delta finds its own positions untouched — no order between lanes or steps is needed).
+        //      A quality of 128 or more at a shared position would carry between bytes: such a family is voted out BEFORE the first store (a
+        //      family of several steps: in a pass over the qualities of its own) and takes the byte-wise steps below.
+        const uint32_t oo1 = rlane(ov_off1, fp), oo2 = rlane(ov_off2, fp);
+        if ((KA::of(P).s2_packed & 8u) && ov_uniform && np > 1u && (oo1 == 0u || oo2 == 0u) && ((QS & 7u) | (SS & 3u)) == 0u && min_bq <= 128u) {
+          if (act && ov_cnt != 0) *(uint16_t*)(W + ibase + 2u * (uint32_t)__popcll(om & below)) = (uint16_t)(slot | (mate_slot << 8));   // pair -> its two rows
+          wave_sync();
+          const bool a_is_1 = oo1 == 0u;                         // the aligned mate ("A") is the pair's first row
+          const uint32_t off = oo1 | oo2, sq = off & 3u, sn = off & 7u;   // the other mate ("B") starts here
+          const uint32_t ng = (cn0 + 7u) >> 3, total = np * ng;  // (at most 31 pairs x 32 groups: s2_packed_shape)
+          const uint32_t inv = uni((uint32_t)(1048576.0f / (float)ng) + 2u);    // (t * inv) >> 20 == t / ng for t < 32 * 64, as below
+          const uint32_t mb4 = min_bq * 0x01010101u;
+          // one lane's item: the addresses of A's words and of B's first aligned words, the in-range masks, the eight positions of both mates.
+          // B's second sequence word and third quality dword may lie past its row — in the next row, or in the 16 bytes between the tile and
+          // the pair table —: every position in them then lies past the read, is masked out of the arithmetic and gets a delta of 0.
+          struct OvLane { uint32_t aq, as, bq, bs, ml, mh, qax, qay, caw, qbx, qby, cbp; };
+          auto ov_load = [&](const uint32_t t0, OvLane& L) {
+            const uint32_t t = t0 + lane;
+            const bool in = t < total;
+            const uint32_t tt = in ? t : 0u;                     // (a lane past the index space computes item 0 under empty masks and stores nothing)
+            const uint32_t pi = s2_mul24(tt, inv) >> 20, k = tt - s2_mul24(pi, ng);
+            const uint32_t rows = *(const uint16_t*)(W + ibase + 2u * pi), r1 = rows & 0xFF, r2 = rows >> 8;
+            const uint32_t rA = a_is_1 ? r1 : r2, rB = a_is_1 ? r2 : r1;
+            L.aq = rA * QS + 8u * k; L.as = S0 + rA * SS + 4u * k;
+            L.bq = rB * QS + 4u * ((off >> 2) + 2u * k); L.bs = S0 + rB * SS + 4u * ((off >> 3) + k);
+            pk::ov_in_masks(in ? cn0 : 0u, k, &L.ml, &L.mh);
+            const uint2 qa = *(const uint2*)(W + L.aq);
+            L.qax = qa.x; L.qay = qa.y; L.caw = *(const uint32_t*)(W + L.as);
+            pk::ov_gather_q(*(const uint32_t*)(W + L.bq), *(const uint32_t*)(W + L.bq + 4u), *(const uint32_t*)(W + L.bq + 8u), sq, &L.qbx, &L.qby);
+            L.cbp = pk::ov_gather_c(*(const uint32_t*)(W + L.bs), *(const uint32_t*)(W + L.bs + 4u), sn);
+          };
+          if (total > 64u) {
+            uint32_t hi_v = 0;
+            for (uint32_t t0 = 0; t0 < total; t0 += 64) { OvLane L; ov_load(t0, L); hi_v |= pk::ov_high(L.qax, L.qay, L.qbx, L.qby, L.ml, L.mh) ? 1u : 0u; }
+            ov_guard = __any(hi_v != 0u);
+          }
+          if (!ov_guard) {
+            uint32_t n_ad = 0, n_chg = 0;                        // per lane: agreements | disagreements << 16 (a family has fewer than 2^13 shared bases), changed agreements
+            for (uint32_t t0 = 0; t0 < total; t0 += 64) {
+              OvLane L;
+              ov_load(t0, L);
+              if (total <= 64u && __any(pk::ov_high(L.qax, L.qay, L.qbx, L.qby, L.ml, L.mh))) { ov_guard = true; break; }   // (the only step: nothing stored yet)
+              pk::OvStep R;
+              pk::ov_step(L.qax, L.qay, L.caw, L.qbx, L.qby, L.cbp, L.ml, L.mh, mb4, R);
+              uint32_t e[3], f[2];
+              pk::ov_scatter_q(R.dq[0], R.dq[1], sq, e); pk::ov_scatter_c(R.dc, sn, f);
+              if (t0 + lane < total) {
+                *(uint2*)(W + L.aq) = make_uint2(R.qa[0], R.qa[1]); *(uint32_t*)(W + L.as) = R.ca;
+                atomicXor((uint32_t*)(W + L.bq), e[0]); atomicXor((uint32_t*)(W + L.bq + 4u), e[1]); atomicXor((uint32_t*)(W + L.bq + 8u), e[2]);
+                atomicXor((uint32_t*)(W + L.bs), f[0]); atomicXor((uint32_t*)(W + L.bs + 4u), f[1]);
+              }
+              n_ad += R.n_ad; n_chg += R.n_chg;
+            }
+            if (!ov_guard) {
+              const uint32_t t_ad = wave_sum(n_ad), t_chg = wave_sum(n_chg);
+              ov_agree = t_ad & 0xFFFFu; ov_dis = t_ad >> 16; ov_corr = t_chg + 2u * ov_dis;
+              ov_packed = true;
+            }
+          }
+        }
+      }
+      if (ov_packed) {
+        // (corrected above)
+      } else if (ov_uniform && np > 1u && cn0 < 64u) {
         // ONE geometry for every pair: pairs x shared bases as one index space, 64 per step (8 pairs x 40 bases = 5 steps, not 8)
         const uint32_t oo1 = rlane(ov_off1, fp), oo2 = rlane(ov_off2, fp);
         if (act && ov_cnt != 0) *(uint16_t*)(W + ibase + 2u * (uint32_t)__popcll(om & below)) = (uint16_t)(slot | (mate_slot << 8));   // pair -> its two rows
@@ -886,6 +956,9 @@ __device__ __forceinline__ void s2_cols_family(const FastParams& P, const uint32
           for (uint32_t w0 = 0; w0 < cn; w0 += 64, o1 += 32, o2 += 32, q1 += 64, q2 += 64) shared_base(w0 + lane < cn, o1, o2, q1, q2, sh1, sh2);
         }
       }
+      // (packed build) which step corrected the family, for k_split_finish's counters: in the top bits of ov_corr, a uniform that lives to the
+      // family's result anyway (fastpath.h, S2_OV_*) — a register of its own would sit in a spill lane across the column pass
+      if constexpr (COLS == 1) ov_corr |= ov_packed ? S2_OV_PACKED : ov_guard ? (S2_OV_BYTEWISE | S2_OV_GUARD) : S2_OV_BYTEWISE;
     }
   }
   const uint32_t ov_bases = ov_agree + ov_dis;
@@ -1654,6 +1727,7 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
   const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63;
   uint32_t c_total = 0, c_cons = 0, c_insuf = 0, c_zero = 0, c_orphan = 0, c_agree = 0, c_dis = 0, c_corr = 0, c_packed = 0, c_classic = 0, c_clean = 0;
+  uint32_t c_ovp = 0, c_ovb = 0, c_ovg = 0;                 // (fgx_debug_last_packed_overlap: the packed build's families with overlapping mates by the step that corrected them)
   uint32_t c_apply = 0, c_cut = 0, c_over = 0;               // (fgx_debug_last_full_results: families whose answers the pair writer applies / refused because their items are not in one piece)
   if (gi < count) {
     const uint32_t g = P.group_list ? P.group_list[gi] : P.g0 + gi;
@@ -1673,7 +1747,8 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
       c_packed = padded ? 1u : 0u; c_classic = padded ? 0u : 1u; c_clean = (padded && clean) ? 1u : 0u;
       c_total = O.n; c_cons = O.ne;
       c_insuf = O.rej & 0xFF; c_zero = (O.rej >> 8) & 0xFF; c_orphan = O.rej >> 16;
-      c_agree = O.ov_agree; c_dis = O.ov_dis; c_corr = O.ov_corr;
+      c_agree = O.ov_agree; c_dis = O.ov_dis; c_corr = O.ov_corr & S2_OV_COUNT;
+      if (padded) { c_ovp = (O.ov_corr & S2_OV_PACKED) ? 1u : 0u; c_ovb = (O.ov_corr & S2_OV_BYTEWISE) ? 1u : 0u; c_ovg = (O.ov_corr & S2_OV_GUARD) ? 1u : 0u; }
       const uint4 fd = P.fam_desc[g];
       const unsigned long long lo_off = (unsigned long long)fd.x | ((unsigned long long)fd.y << 32);
       const uint32_t r0 = P.grp_first[g];
@@ -1817,6 +1892,7 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
   const uint32_t t_agree = wave_sum(c_agree), t_dis = wave_sum(c_dis), t_corr = wave_sum(c_corr);
   const uint32_t t_packed = wave_sum(c_packed), t_classic = wave_sum(c_classic);   // (diagnostics, fgx_debug_last_split_builds: which build finished how many families)
   const uint32_t t_clean = wave_sum(c_clean);                                       // (fgx_debug_last_packed_rows: the packed build's families by row loop)
+  const uint32_t t_ovp = wave_sum(c_ovp), t_ovb = wave_sum(c_ovb), t_ovg = wave_sum(c_ovg);   // (fgx_debug_last_packed_overlap: ... by the step that corrected their overlapping mates)
   if (lane == 0) {
     unsigned long long* st = P.stats + (size_t)((blockIdx.x * 4 + (threadIdx.x >> 6)) & (STAT_SLOTS - 1)) * 32;
     if (t_total) atomicAdd(&st[0], (unsigned long long)t_total);
@@ -1834,6 +1910,12 @@ __global__ __launch_bounds__(256) void k_split_finish(FastParams P, uint32_t cou
     if (t_classic) atomicAdd(&st[29], (unsigned long long)t_classic);
     if (t_clean) atomicAdd(&st[30], (unsigned long long)t_clean);
     if (t_packed - t_clean) atomicAdd(&st[31], (unsigned long long)(t_packed - t_clean));
+    if (t_ovp | t_ovb) {     // (the slots of the result counters, behind them: the 32 words of a slot above are taken)
+      unsigned long long* fs = P.full_stats + (size_t)((blockIdx.x * 4 + (threadIdx.x >> 6)) & (STAT_SLOTS - 1)) * FULL_STATS_STRIDE + FULL_STATS_N;
+      if (t_ovp) atomicAdd(&fs[0], (unsigned long long)t_ovp);
+      if (t_ovb) atomicAdd(&fs[1], (unsigned long long)t_ovb);
+      if (t_ovg) atomicAdd(&fs[2], (unsigned long long)t_ovg);
+    }
   }
   if (P.full_results) {
     const uint32_t t_apply = wave_sum(c_apply), t_cut = wave_sum(c_cut), t_over = wave_sum(c_over);
