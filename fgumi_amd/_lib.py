@@ -86,7 +86,8 @@ EXPORTS = ["fgx_options_default", "fgx_create", "fgx_destroy", "fgx_last_error",
            "fgx_filter_records", "fgx_filter_records_device", "fgx_filter_last_output_device",
            "fgx_record_boundaries_device", "fgx_inflate_block_host", "fgx_inflate_block_two_phase_host", "fgx_deflate_block_host", "fgx_run_bam", "fgx_run_bam_rejects", "fgx_bgzf_inflate_device_bench", "fgx_bgzf_deflate_device_bench", "fgx_bgzf_recompress_file", "fgx_pipeline_last_error",
            "fgx_set_reference", "fgx_methylation_annotate_host", "fgx_methylation_runs_host", "fgx_methylation_mm_ml_host", "fgx_canon_duplex_host", "fgx_canon_duplex_runs_host", "fgx_canon_simplex_host", "fgx_canon_codec_host", "fgx_simplex_rejects_host", "fgx_strand_rejects_host", "fgx_balanced_shards", "fgx_regenerate_alignment_tags_host",
-           "fgx_debug_last_duplex_deep", "fgx_debug_last_duplex_deep_capped", "fgx_debug_last_boundary_rounds"]
+           "fgx_debug_last_duplex_deep", "fgx_debug_last_duplex_deep_capped", "fgx_debug_last_boundary_rounds",
+           "fgx_debug_last_codec_deep", "fgx_debug_last_codec_deep_capped"]
 
 _lib = None
 
@@ -211,6 +212,10 @@ def load():
     if hasattr(L, "fgx_debug_last_duplex_deep_capped"):     # (likewise: a library built before the CAP builds of duplex_deep.inc)
         L.fgx_debug_last_duplex_deep_capped.argtypes = [VP]
         L.fgx_debug_last_duplex_deep_capped.restype = U32
+    for name in ("fgx_debug_last_codec_deep", "fgx_debug_last_codec_deep_capped"):   # (likewise: a library built before codec_deep.inc)
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [VP]
+            getattr(L, name).restype = U32
     if hasattr(L, "fgx_debug_last_boundary_rounds"):        # (likewise: a library built before this export)
         L.fgx_debug_last_boundary_rounds.argtypes = [VP]
         L.fgx_debug_last_boundary_rounds.restype = U32

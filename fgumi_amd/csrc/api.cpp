@@ -1507,6 +1507,8 @@ uint32_t fgx_debug_last_deep_families(const fgx_caller* c) { return (c && c->fas
 uint32_t fgx_debug_last_wide_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_wide_families : 0u; }
 uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_duplex_deep : 0u; }
 uint32_t fgx_debug_last_duplex_deep_capped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_duplex_deep_capped : 0u; }
+uint32_t fgx_debug_last_codec_deep(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_codec_deep : 0u; }
+uint32_t fgx_debug_last_codec_deep_capped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_codec_deep_capped : 0u; }
 // repair rounds of the last fgx_record_boundaries_device call (boundaries.hip: 0 = every segment's guess was right)
 uint32_t fgx_debug_last_boundary_rounds(const fgx_caller* c) { return c ? c->last_boundary_rounds : 0u; }
 // the split pipeline's first stage in the last device batch: out4[0] families finished by k_split_cols's packed build, [1] by its classic builds

@@ -310,11 +310,15 @@ struct FastPath {
   uint32_t last_big_families = 0;          // ... in the last batch
   uint32_t last_deep_families = 0;         // ... of which k_deep_parse + k_deep_cols (simplex_deep.inc) took
   DevBuf d_deep_sizes, d_deep_row0, d_deep_rows, d_deep_fams, d_deep_out, d_deep_out2;
-  DevBuf d_deep_walk;                      // duplex_deep.inc under --max-reads-per-strand: the scoring rows of capped sets in walk order (allocated for a caller with a cap)
+  DevBuf d_deep_walk;                      // duplex_deep.inc under --max-reads-per-strand: the scoring rows of capped sets in walk order (allocated for a caller with a cap);
+                                           // codec_deep.inc: the RX values of a molecule's records in file order
   uint32_t last_duplex_deep = 0;           // duplex molecules of more than 64 records that k_duplex_deep_parse + k_duplex_deep_cols (duplex_deep.inc) decided in the last batch;
                                            // not counted into last_big_families / last_deep_families (the simplex path's).  They use d_big and the d_deep_* buffers.
   uint32_t last_duplex_deep_capped = 0;    // ... of which a --max-reads-per-strand bit a set (the CAP builds; FGX_DUPLEX_DEEP_CAP=1)
-  bool canon_second_pass = false;          // set by the caller around the `run` of a canonical second pass: duplex_deep.inc stays off there
+  uint32_t last_codec_deep = 0;            // CODEC molecules of more than 64 records that k_codec_deep_parse + k_codec_deep_cols (codec_deep.inc; FGX_CODEC_DEEP=1) decided in the
+                                           // last batch; likewise not counted into the simplex path's counters.  They use d_big, the d_deep_* buffers and d_deep_walk (the RX list).
+  uint32_t last_codec_deep_capped = 0;     // ... of which a --max-reads-per-strand dropped a read (the CAP builds of the record kernel)
+  bool canon_second_pass = false;          // set by the caller around the `run` of a canonical second pass: duplex_deep.inc and codec_deep.inc stay off there
   bool rejects_pass = false;               // set by the host entry around the device pass of a --rejects batch (which runs with the option cleared): off there too
   uint32_t last_wide_families = 0;         // ... and of what those left, the wide kernels (simplex_wide.inc; FGX_DEEP_WIDE=1) took — not counted into last_deep_families
   DevBuf d_wide_scratch, d_wide_pass, d_wide_pass0, d_wide_depth;   // k_wide_parse's per-record state, the families' column passes and their scan, the passes' depth extremes

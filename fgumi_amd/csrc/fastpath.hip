@@ -1210,7 +1210,7 @@ __global__ __launch_bounds__(256, MODE == 1 ? FGX_WAVE_OCC_DUPLEX : FGX_WAVE_OCC
   // simplex families go to the workgroup-per-family kernel, duplex / CODEC molecules to the general path
   auto to_retry = [&]() { if (!P.retry) { to_defer(); return; } if (lane == 0) { uint32_t k = atomicAdd(P.n_retry, 1u); P.retry[k] = g; } };
   if (!bail && n > 64) {
-    if ((MODE == 0 || MODE == 1) && P.big) { if (lane == 0) { uint32_t k = atomicAdd(P.n_big, 1u); P.big[k] = g; } }   // k_family's, directly (duplex: duplex_deep.inc's list)
+    if (P.big) { if (lane == 0) { uint32_t k = atomicAdd(P.n_big, 1u); P.big[k] = g; } }   // k_family's, directly (duplex: duplex_deep.inc's list; CODEC: codec_deep.inc's)
     else if (MODE == 0) to_retry();
     else to_defer();
     bail = true;
@@ -2842,6 +2842,7 @@ __global__ __launch_bounds__(256) void k_call_full(FullParams P) {
 #include "simplex_split.inc"
 #include "simplex_deep.inc"
 #include "duplex_deep.inc"
+#include "codec_deep.inc"
 #include "simplex_wide.inc"
 #include "duplex_meth.inc"
 
@@ -2946,7 +2947,7 @@ enum MiscWord : uint32_t {
   MISC_SMALL_RECS = 35,      // records in families of at most 64 records (k_col_bound)
   MISC_DIR_FLAGS = 36,       // direct records: low half families whose records differ in size from the prediction, high half records past the room
   MISC_N_BIG = 37,           // families of more than 64 records: k_family's list
-  MISC_N_DEEP = 38,          // families a pass of the streaming kernels hands on; duplex_deep.inc: low half the molecules it decided, high half those of them a strand cap bit
+  MISC_N_DEEP = 38,          // families a pass of the streaming kernels hands on; duplex_deep.inc / codec_deep.inc: low half the molecules it decided, high half those of them a strand cap bit
   MISC_BUILD_FAMILIES = 40,  // [40, 44): the slots' diagnostics (k_reduce_stats): families finished by k_split_cols's packed build, by its classic builds, by the packed build's clean / general row loop
   MISC_N_SLOW = 44,          // duplex / CODEC: records the fast writer leaves to the per-field kernel
   MISC_FULL_RESULTS = 46,    // [46, 51): items answered through the result array, items scattered, families the writer applies, families refused as not in one piece, families refused for more than 64 items
@@ -3003,6 +3004,8 @@ struct BatchSwitches {     // read at the start of every batch: tests and tools 
   const bool deep_wide = deep_wide_env && deep_wide_env[0] && deep_wide_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the wide kernels behind the streaming ones (simplex_wide.inc)
   const char* const duplex_deep_cap_env = getenv("FGX_DUPLEX_DEEP_CAP");
   const bool duplex_deep_cap = duplex_deep_cap_env && duplex_deep_cap_env[0] && duplex_deep_cap_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the CAP builds of duplex_deep.inc
+  const char* const codec_deep_env = getenv("FGX_CODEC_DEEP");
+  const bool codec_deep = codec_deep_env && codec_deep_env[0] && codec_deep_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): CODEC molecules of more than 64 records on the device (codec_deep.inc)
   const uint32_t seg_bytes = env_in(fgx_knob("FGX_SEG_BYTES"), 4096, 32768, 11776) & ~63u;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
   const uint32_t wave_bytes = env_in(fgx_knob("FGX_WAVE_BYTES"), 1024, 22016, 0) & ~15u;     // tuning knobs (0: the FastPath's own value)
   const uint32_t lds_tile_large = env_in(fgx_knob("FGX_LDS_TILE_LARGE"), 16384, 163840, 0) & ~15u;
@@ -3079,6 +3082,10 @@ struct Batch {
   const bool dup_deep = duplex && sw.duplex_deep && !o.trim && !o.track_rejects && !fp.rejects_pass && !meth_dup && !fp.canon_second_pass;
   // ... and their CAP builds, which decide a --max-reads-per-strand that bites a set of such a molecule (FGX_DUPLEX_DEEP_CAP=1; off: it is deferred)
   const bool dup_deep_cap = dup_deep && dup_cap && sw.duplex_deep_cap;
+  // CODEC molecules of more than 64 records (codec_deep.inc; FGX_CODEC_DEEP=1): k_family_wave<2> lists them instead of deferring them, and k_codec_deep_parse +
+  // k_codec_deep_cols decide the list — up to 254 records.  Not under --trim or --rejects, not in the canonical second pass.  (The CODEC caller has no
+  // methylation-aware mode, and the host keeps non-default duplex-disagreement thresholds off the whole device path.)
+  const bool codec_deep = codec && sw.codec_deep && !o.trim && !o.track_rejects && !fp.rejects_pass && !fp.canon_second_pass;
   // Simplex without --trim: which head of the launch chain?  Shallow families (the mean family fits a quarter of a wave's LDS
   // slice) start at k_simplex_seg<4>; everything else at the split pipeline (k_split_parse + k_split_cols, simplex_split.inc),
   // whose record kernel also leaves what k_col_bound would (column bound, byte-span descriptor).
@@ -3149,7 +3156,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
-    if (!fp.canon_second_pass) fp.last_duplex_deep = fp.last_duplex_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
+    if (!fp.canon_second_pass) fp.last_duplex_deep = fp.last_duplex_deep_capped = fp.last_codec_deep = fp.last_codec_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
     fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_packed_overlap) v = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
@@ -3319,7 +3326,7 @@ struct Batch {
     // (not with direct records: their merge pass walks ONE list of the families that left the split pipeline — the route list)
     if (!duplex && !codec && !direct) { fp.d_big.reserve((size_t)n_grp * 4); P.big = fp.d_big.as<uint32_t>(); P.n_big = cnt(MISC_N_BIG); }
     // duplex molecules of more than 64 records: k_family_wave<1> lists them for the kernels of duplex_deep.inc (without the list it defers them)
-    if (dup_deep) { fp.d_big.reserve((size_t)n_grp * 4); P.big = fp.d_big.as<uint32_t>(); P.n_big = cnt(MISC_N_BIG); }
+    if (dup_deep || codec_deep) { fp.d_big.reserve((size_t)n_grp * 4); P.big = fp.d_big.as<uint32_t>(); P.n_big = cnt(MISC_N_BIG); }   // (CODEC: k_family_wave<2>, codec_deep.inc)
     n_cur = meth_dev ? 0u : n_grp;       // (methylation-aware mode: no wavefront-per-family kernel runs)
   }
 
@@ -3339,7 +3346,7 @@ struct Batch {
       FastParams PS = stage_params(st[i].bytes, i + 1 < st.size() || keep_last);
       launch(st[i], PS);
       uint32_t n_next = 0;
-      if (dup_deep) {   // the count of listed deep molecules travels with the copy the chain waits for anyway (the split stages' window: retry .. big)
+      if (dup_deep || codec_deep) {   // the count of listed deep molecules travels with the copy the chain waits for anyway (the split stages' window: retry .. big)
         unsigned long long h_cnt[MISC_SPLIT_WINDOW] = {};
         hip_check(hipMemcpyAsync(h_cnt, misc + MISC_N_RETRY, sizeof(h_cnt), hipMemcpyDeviceToHost, s), "D2H");
         sync();
@@ -3608,6 +3615,44 @@ struct Batch {
       FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_cols<0>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
     }
     dup_deep_ran = true;   // (the count of decided molecules comes back with the batch's counters)
+  }
+
+  // ---- deep CODEC molecules (codec_deep.inc): the list k_family_wave<2> filled (run_slices read its count into n_dup_deep, the one counter of listed deep
+  //      molecules) — sizes, scan, the record kernel in its two builds, the column kernel.  What they do not take is on the deferred list when they are done:
+  //      from there the canonical second pass or the general path, as before.  A batch without such a molecule launches nothing and waits for nothing here ----
+  bool codec_deep_ran = false;
+  void codec_deep_molecules() {
+    if (!codec_deep || !n_dup_deep) return;
+    const uint32_t* const list = fp.d_big.as<uint32_t>();
+    const uint32_t n_list = n_dup_deep;
+    fp.d_deep_sizes.reserve((size_t)n_list * 8 + 64); fp.d_deep_row0.reserve((size_t)n_list * 8 + 64);
+    FGX_LAUNCH(k_deep_sizes, dim3((n_list + 255) / 256), dim3(256), 0, s, list, n_list, d_grp_first, fp.d_deep_sizes.as<uint64_t>());
+    scan_u64(fp.d_deep_sizes.as<uint64_t>(), fp.d_deep_row0.as<uint64_t>(), n_list, "scan of the deep molecules' records");
+    uint64_t lastr[2] = {0, 0};
+    hip_check(hipMemcpyAsync(&lastr[0], fp.d_deep_row0.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    hip_check(hipMemcpyAsync(&lastr[1], fp.d_deep_sizes.as<uint64_t>() + (n_list - 1), 8, hipMemcpyDeviceToHost, s), "D2H");
+    sync();
+    const uint64_t n_rows = lastr[0] + lastr[1];
+    if (n_rows > (uint64_t)n_rec) throw std::runtime_error("device pipeline: " + std::to_string(n_rows) + " rows for the deep CODEC kernels, more than the batch has records");
+    // a molecule of n records holds at most n rows and at most n RX values (d_deep_walk: the RX list, 8 bytes an entry)
+    fp.d_deep_rows.reserve((size_t)n_rows * sizeof(DeepRow) + 64); fp.d_deep_fams.reserve((size_t)n_list * sizeof(CodecDeepMol) + 64);
+    fp.d_deep_walk.reserve((size_t)n_rows * 8 + 64);
+    hip_check(hipMemsetAsync(cnt(MISC_N_DEEP), 0, 8, s), "memset");   // (both halves of the word: decided molecules, of which capped)
+    CodecDeepParams DP;
+    DP.list = list; DP.n_list = n_list; DP.row0 = fp.d_deep_row0.as<uint64_t>();
+    DP.rows = fp.d_deep_rows.as<DeepRow>(); DP.mols = fp.d_deep_fams.as<CodecDeepMol>(); DP.umi = fp.d_deep_walk.as<unsigned long long>(); DP.n_done = cnt(MISC_N_DEEP);
+    FastParams PD = P;
+    PD.group_list = nullptr;
+    // (both builds over the whole list: a workgroup whose molecule is the other build's returns at once; the CAP builds for a caller with a cap, as k_family_wave<2, 0, 1>)
+    if (o.codec_max_reads_per_strand > 0) {
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_codec_deep_parse<128, 128, 1>), dim3(n_list), dim3(128), 0, s, PD, DP);
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_codec_deep_parse<256, 256, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    } else {
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_codec_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
+      FGX_LAUNCH(HIP_KERNEL_NAME(k_codec_deep_parse<256, 256>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    }
+    FGX_LAUNCH(k_codec_deep_cols, dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
+    codec_deep_ran = true;   // (the counts of decided molecules come back with the batch's counters)
   }
 
   // ---- deep families: k_deep_parse + k_deep_cols (simplex_deep.inc) take the big list; what is outside their shape goes on to k_family ----
@@ -3926,6 +3971,7 @@ struct Batch {
     res->n_deferred = (uint32_t)(h_misc[MISC_N_DEFERRED] & 0xFFFFFFFFull);
     fp.last_meth_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] & 0xFFFFFFFFull);
     if (dup_deep_ran) { fp.last_duplex_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_duplex_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
+    if (codec_deep_ran) { fp.last_codec_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_codec_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
     res->d_deferred = fp.d_deferred.as<uint32_t>();
     res->d_out_off = fp.d_offsets.as<uint64_t>();
     res->d_slot_size = fp.d_sizes.as<uint64_t>();
@@ -3956,6 +4002,7 @@ int run_once(FastPath& fp, fgx_caller* c, const uint8_t* d_blob, uint64_t blob_l
   if (b.simplex_v2) b.wave2_chain();
   b.family_wave_stages();
   b.duplex_deep_molecules();
+  b.codec_deep_molecules();
   b.deep_families();
   b.workgroup_families();
   if (const int rc = b.call_full()) return rc;

@@ -480,6 +480,15 @@ uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c);
 /* ... and how many of those molecules a --max-reads-per-strand bit: decided by the CAP builds of the two kernels, which a caller with a cap > 0
  * launches under FGX_DUPLEX_DEEP_CAP=1 (default off: such a molecule is deferred).  Always <= fgx_debug_last_duplex_deep. */
 uint32_t fgx_debug_last_duplex_deep_capped(const fgx_caller* c);
+/* Diagnostics of the last device batch of `c`: CODEC molecules of more than 64 records that the streaming CODEC kernels
+ * (fgumi_amd/csrc/codec_deep.inc: k_codec_deep_parse + k_codec_deep_cols) decided — up to 254 records (127 templates), every record a paired primary
+ * read with one M/=/X op, mates adjacent.  The path runs only under FGX_CODEC_DEEP=1 (read per batch, default off: such molecules are deferred to the
+ * general path), and not under --trim, --rejects or in the canonical second pass.  0 for a caller that has run no device batch, and for a caller
+ * that is not the CODEC caller. */
+uint32_t fgx_debug_last_codec_deep(const fgx_caller* c);
+/* ... and of how many of those molecules a --max-reads-per-strand dropped a read (the CAP builds of the record kernel, launched for a caller with
+ * a cap > 0).  Always <= fgx_debug_last_codec_deep. */
+uint32_t fgx_debug_last_codec_deep_capped(const fgx_caller* c);
 /* Repair rounds of the last fgx_record_boundaries_device call on `c` (0 = every segment's guess was right; fgx_run_bam sums them into boundary_repair_rounds). */
 uint32_t fgx_debug_last_boundary_rounds(const fgx_caller* c);
 
