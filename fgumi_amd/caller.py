@@ -345,6 +345,13 @@ class _HandleCaller(ConsensusCaller):
         streaming kernels of deep families hold; up to 16 384 records)."""
         return int(lib.fgx_debug_last_wide_families(self._h))
 
+    @property
+    def last_deep_clipped(self) -> int:
+        """Simplex families / duplex molecules of more than 64 records of the last device batch that hold a soft- / hard-clipped record (more than one
+        CIGAR op) and that the clip-taking builds of the streaming record kernels accepted (FGX_DEEP_CLIPS=1, outside the methylation-aware mode; 0 with
+        the switch unset).  Counted where the record kernel accepts the group: the column kernel may still hand it on (an RX failure, a full item pool)."""
+        return int(lib.fgx_debug_last_deep_clipped(self._h))
+
     def set_general_only(self, on: bool = True):
         """Route every family through the general host-orchestrated path (default: device-resident fast
         path, general path only for the families it defers)."""

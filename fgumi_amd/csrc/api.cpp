@@ -1503,6 +1503,7 @@ uint32_t fgx_debug_last_meth_device(const fgx_caller* c) { return (c && c->fast)
 // ... of which held a record of more than one CIGAR op (soft / hard clips around one aligned block) and were decided by the device kernels — counted
 // there, read back with the batch's other counters
 uint32_t fgx_debug_last_meth_clipped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_meth_clipped : 0u; }
+uint32_t fgx_debug_last_deep_clipped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_clipped : 0u; }
 uint32_t fgx_debug_last_deep_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_families : 0u; }
 uint32_t fgx_debug_last_wide_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_wide_families : 0u; }
 uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_duplex_deep : 0u; }

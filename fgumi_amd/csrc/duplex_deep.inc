@@ -38,7 +38,7 @@
 // of 32 consecutive bytes at `base + 32 j`, issued a batch ahead of their use, and an index list would put a second, dependent scalar load in front of each
 // of them (load the index, wait, load the row), while the copies cost one more 32-byte store per scoring read in a kernel that already writes the row.
 //
-// Outside the shape — the molecule leaves for the deferred list, as it did from k_family_wave<1>: an indel or a clip (more than one CIGAR op), a secondary or
+// Outside the shape — the molecule leaves for the deferred list, as it did from k_family_wave<1>: an indel (any I D N P op), a clip without the CLIPS builds (more than one CIGAR op; with them more than WG_CIG_OPS ops or no aligned block), a secondary or
 // supplementary record, an unmapped read, an MC the closed-form mate clip does not take, no `/A` | `/B` on a paired record, absent qualities, a paired
 // record that is FIRST and LAST, a --max-reads-per-strand that bites a set (without the CAP builds, and a cap of 0 with them), a side above the bound, more than DEEP_MAX records, RX of unequal length or
 // above FAST_RX_CAP, an IUPAC code in a lone read, an overflow of the FullItem pool.  The host launches nothing of this under --trim, --rejects, in the
@@ -77,8 +77,9 @@ struct DuplexDeepParams {
 
 // DeepRow::w[7] of a duplex row: bit 2 of the flags byte = the read's FIRST flag (the halves of a paired UMI are flipped for reads whose FIRST flag differs
 // from the record's); bits 0 / 1 as in simplex_deep.inc (reverse strand, carries RX)
-template <uint32_t MAXR>
-struct DuplexDeepLds : DeepLds<MAXR> {
+// <CLIPS>: on DeepClipLds (lead / aln / tot per record and `multi`) for the clip-taking build of the record kernel
+template <uint32_t MAXR, int CLIPS = 0>
+struct DuplexDeepLds : DeepLdsOf<MAXR, CLIPS>::type {
   uint16_t mi_rel[MAXR];                 // MI value offset inside the record body
   uint8_t mi_len[MAXR];
   uint8_t dup[MAXR];                     // strand (0 none, 1 /A, 2 /B) | paired << 2 | FIRST << 3
@@ -91,9 +92,16 @@ struct DuplexDeepLds : DeepLds<MAXR> {
 // <NT, MAXR>: <128, 128> takes the listed molecules of up to 128 records, <256, DEEP_MAX> the larger ones — both are launched over the whole list and a
 // workgroup whose molecule is the other build's returns at once (no hand-over list, no host synchronisation between them).  Thread = record: a 66-record
 // molecule in the 256-thread build would leave three of its four wavefronts without a record (DESIGN.md §4 has the figures).
-template <uint32_t NT, uint32_t MAXR, int CAP = 0>
+//
+// <CLIPS> 1 (launched under FGX_DEEP_CLIPS=1 in place of the CLIPS 0 build): reads with soft / hard clips around one aligned block (H* S* (M|=|X)+ S* H*, up to
+// WG_CIG_OPS ops) are in the shape.  The reference calls such a read in query space like any other, so the rows and the column kernel see no difference; what
+// the clips change is deep_parse_records<1>'s — the mate clip by the general rule on the ops — and the shared span of a pair in step 2: the ALIGNED blocks
+// overlap, the leading clip goes into both query offsets (k_deep_parse<.., .., 1> step 2; k_family_wave<1, 1> restates the same for a wavefront).  A molecule
+// with a multi-op record that this kernel accepts counts into deep_clipped_counter (fgx_debug_last_deep_clipped: "accepted by the record kernel" — the column
+// kernel may still hand the molecule on for an RX failure or a full item pool).  CLIPS 0 is the kernel without any of it.
+template <uint32_t NT, uint32_t MAXR, int CAP = 0, int CLIPS = 0>
 __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDeepParams D) {
-  __shared__ DuplexDeepLds<MAXR> S;
+  __shared__ DuplexDeepLds<MAXR, CLIPS> S;
   __shared__ __align__(16) uint8_t sTagCls[256];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t li = blockIdx.x;
@@ -104,6 +112,7 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
   fill_tag_classes(sTagCls);
   if (tid == 0) {
     S.bad = 0; S.ov_agree = S.ov_dis = S.ov_corr = 0;
+    if constexpr (CLIPS != 0) S.multi = 0;
     S.n_paired = 0; S.n_zero = 0; S.first_paired = 0xFFFFFFFFu;
     for (int e = 0; e < 2; e++) { S.any_strand[e] = S.pair_cnt[e] = S.r1_cnt[e] = S.grp_n[e] = S.grp_rev[e] = 0; S.first_of[e] = 0xFFFFFFFFu; }
     for (int k = 0; k < 4; k++) { S.set_rem[k] = 0; S.set_len[k] = 0; }
@@ -115,7 +124,7 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
   const uint32_t min_bq = P.min_input_bq & 0xFFu;
 
   // ---- 1. parse: thread = record (k_simplex_wave2's record shape; an unmapped record is not in it here: the duplex caller needs a strand for every read) ----
-  deep_parse_records<0>(P, S, S, r0, n, tid, NT, sTagCls, false);
+  deep_parse_records<CLIPS>(P, S, S, r0, n, tid, NT, sTagCls, false);
   __syncthreads();
   if (S.bad) { leave(); return; }
   // the duplex rules of k_family_wave<1> phase 2: the strand from the MI suffix; every paired record needs `<id>/A` or `<id>/B` (duplex_caller.rs:2557-2566)
@@ -174,10 +183,17 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
       if (clater >= 0) continue;                            // a later R1 carries the name: this one is not paired
       const uint32_t b = (uint32_t)cmate;
       if (S.ref_id[a] != S.ref_id[b]) continue;
-      const int32_t s1 = S.pos[a] + 1, e1 = S.pos[a] + (int32_t)S.l_seq[a], s2 = S.pos[b] + 1, e2 = S.pos[b] + (int32_t)S.l_seq[b];
+      // (CLIPS: the aligned blocks share reference positions; a leading clip shifts the block's query offset.  The CLIPS 0 build has no aln / lead
+      // arrays: it reads l_seq in a statement of its own)
+      int32_t s1, e1, s2, e2;
+      uint32_t qa = 0, qb = 0;
+      if constexpr (CLIPS != 0) {
+        s1 = S.pos[a] + 1; e1 = S.pos[a] + (int32_t)S.aln[a]; s2 = S.pos[b] + 1; e2 = S.pos[b] + (int32_t)S.aln[b];
+        qa = S.lead[a]; qb = S.lead[b];
+      } else { s1 = S.pos[a] + 1; e1 = S.pos[a] + (int32_t)S.l_seq[a]; s2 = S.pos[b] + 1; e2 = S.pos[b] + (int32_t)S.l_seq[b]; }
       const int32_t lox = s1 > s2 ? s1 : s2, hix = e1 < e2 ? e1 : e2;
       if (hix < lox) continue;
-      const uint32_t cnt = (uint32_t)(hix - lox + 1), o1 = (uint32_t)(lox - s1), o2 = (uint32_t)(lox - s2);
+      const uint32_t cnt = (uint32_t)(hix - lox + 1), o1 = (uint32_t)(lox - s1) + qa, o2 = (uint32_t)(lox - s2) + qb;
       S.wo[a] = (uint16_t)o1; S.mo[a] = (uint16_t)o2; S.wc[a] = (uint16_t)cnt; S.partner[a] = (int16_t)b;
       S.wo[b] = (uint16_t)o2; S.mo[b] = (uint16_t)o1; S.wc[b] = (uint16_t)cnt; S.partner[b] = (int16_t)a;
     }
@@ -360,6 +376,7 @@ __global__ __launch_bounds__(NT) void k_duplex_deep_parse(FastParams P, DuplexDe
       f.has_cb = (P.cell0 && (S.bits[fc] & 16u)) ? 1 : 0; f.cb_off = S.cb_rel[fc]; f.cb_len = S.cb_len[fc];
     }
     *M = f;
+    if constexpr (CLIPS != 0) { if (S.multi) atomicAdd(deep_clipped_counter(P), 1u); }   // (no leave() behind this point)
   }
 }
 

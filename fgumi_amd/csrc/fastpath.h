@@ -326,6 +326,7 @@ struct FastPath {
   const void* ref_runs = nullptr;          // methylation-aware mode, the canonical second pass (FGX_METH_CANON=1): canon::RefRuns of every record of the batch `run` is
                                            // about to take, device memory; set by the caller around that one `run`, null otherwise (the records lie where they say)
   uint32_t last_meth_device = 0;           // families of the last batch that the device pipeline decided in the methylation-aware mode
+  uint32_t last_deep_clipped = 0;          // FGX_DEEP_CLIPS=1, outside the mode: families / molecules of more than 64 records with a multi-op record that the clip builds of the streaming record kernels accepted
   uint32_t last_meth_clipped = 0;          // ... of which held a record of more than one CIGAR op (clips around one aligned block) and were not deferred
   uint32_t last_routed = 0;                // families the split pipeline handed to the k_simplex_wave2 chain in the last batch
   uint64_t last_packed_clean = 0, last_packed_general = 0;        // ... of the packed build's: by its clean row loop (no quality read) / by its general one

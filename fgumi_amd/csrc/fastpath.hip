@@ -98,6 +98,10 @@ constexpr int STAT_SLOTS = 1024;        // spread the per-batch counters over ma
 // This holds only while P.n_deferred points at the low half of that 8-byte word of d_misc (fill_params sets it so; a u32 counter uses its word's low
 // half, so the next word's counter is two uint32_t further): whoever points n_deferred elsewhere gives this counter a FastParams member of its own.
 __device__ __forceinline__ uint32_t* meth_clipped_counter(const FastParams& P) { return P.n_deferred + 2; }
+// FGX_DEEP_CLIPS=1, outside the mode: simplex families / duplex molecules of more than 64 records with a record of more than one CIGAR op that the clip builds
+// of the streaming record kernels accepted (fgx_debug_last_deep_clipped).  The HIGH half of the same word, for the same reason; the mode's counter never
+// passes 2^32, and the read-back takes the halves apart.
+__device__ __forceinline__ uint32_t* deep_clipped_counter(const FastParams& P) { return P.n_deferred + 3; }
 
 struct ReadInfo {          // LDS, one per record of the family
   uint64_t goff;           // record body offset in the blob
@@ -2940,7 +2944,7 @@ enum MiscWord : uint32_t {
   MISC_STATS = 0,            // [0, FGX_STATS_LEN): the caller's counters, k_reduce_stats's sums over the slots; [1] = consensus reads written
   MISC_COLS_USED = 28,
   MISC_N_DEFERRED = 29,      // families on the deferred list
-  MISC_N_METH_CLIPPED = 30,  // methylation-aware mode: decided families / molecules with a record of more than one CIGAR op (meth_clipped_counter)
+  MISC_N_METH_CLIPPED = 30,  // methylation-aware mode: decided families / molecules with a record of more than one CIGAR op (meth_clipped_counter); high half: deep_clipped_counter
   MISC_N_RETRY = 31,         // the retry list of the launch under way
   MISC_N_RETRY_OLD = 32,     // k_simplex_wave2 → k_family_wave<0>
   MISC_N_ROUTE = 33,         // k_split_cols → k_simplex_wave2
@@ -3006,6 +3010,8 @@ struct BatchSwitches {     // read at the start of every batch: tests and tools 
   const bool duplex_deep_cap = duplex_deep_cap_env && duplex_deep_cap_env[0] && duplex_deep_cap_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the CAP builds of duplex_deep.inc
   const char* const codec_deep_env = getenv("FGX_CODEC_DEEP");
   const bool codec_deep = codec_deep_env && codec_deep_env[0] && codec_deep_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): CODEC molecules of more than 64 records on the device (codec_deep.inc)
+  const char* const deep_clips_env = getenv("FGX_DEEP_CLIPS");
+  const bool deep_clips = deep_clips_env && deep_clips_env[0] && deep_clips_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the clip-taking builds of k_deep_parse (plain mode) and k_duplex_deep_parse
   const uint32_t seg_bytes = env_in(fgx_knob("FGX_SEG_BYTES"), 4096, 32768, 11776) & ~63u;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
   const uint32_t wave_bytes = env_in(fgx_knob("FGX_WAVE_BYTES"), 1024, 22016, 0) & ~15u;     // tuning knobs (0: the FastPath's own value)
   const uint32_t lds_tile_large = env_in(fgx_knob("FGX_LDS_TILE_LARGE"), 16384, 163840, 0) & ~15u;
@@ -3156,7 +3162,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
-    if (!fp.canon_second_pass) fp.last_duplex_deep = fp.last_duplex_deep_capped = fp.last_codec_deep = fp.last_codec_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
+    if (!fp.canon_second_pass) fp.last_deep_clipped = fp.last_duplex_deep = fp.last_duplex_deep_capped = fp.last_codec_deep = fp.last_codec_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
     fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_packed_overlap) v = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
@@ -3605,13 +3611,24 @@ struct Batch {
     FastParams PD = P;
     PD.group_list = nullptr;
     // (both builds over the whole list: a workgroup whose molecule is the other build's returns at once)
+    // (FGX_DEEP_CLIPS=1: the clip-taking builds of the record kernel in place of the others; the column kernels are the same)
     if (dup_deep_cap) {
-      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128, 1>), dim3(n_list), dim3(128), 0, s, PD, DP);
-      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      if (sw.deep_clips) {
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128, 1, 1>), dim3(n_list), dim3(128), 0, s, PD, DP);
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX, 1, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      } else {
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128, 1>), dim3(n_list), dim3(128), 0, s, PD, DP);
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      }
       FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_cols<1>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
     } else {
-      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
-      FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      if (sw.deep_clips) {
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128, 0, 1>), dim3(n_list), dim3(128), 0, s, PD, DP);
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX, 0, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      } else {
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<128, 128>), dim3(n_list), dim3(128), 0, s, PD, DP);
+        FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_parse<256, DEEP_MAX>), dim3(n_list), dim3(256), 0, s, PD, DP);
+      }
       FGX_LAUNCH(HIP_KERNEL_NAME(k_duplex_deep_cols<0>), dim3((n_list + 3) / 4), dim3(256), 0, s, PD, DP);
     }
     dup_deep_ran = true;   // (the count of decided molecules comes back with the batch's counters)
@@ -3676,8 +3693,12 @@ struct Batch {
     DP.rows = fp.d_deep_rows.as<DeepRow>(); DP.fams = fp.d_deep_fams.as<DeepFam>(); DP.out_list = out; DP.n_out = cnt(MISC_N_DEEP);
     FastParams PD = P;
     PD.group_list = nullptr;
-    // (methylation-aware mode: the clip-taking build of the record kernel, in every size class it runs)
-    if (meth_dev && size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64, 1>), dim3(n_list), dim3(64), 0, s, PD, DP);
+    // (methylation-aware mode: the clip-taking build of the record kernel, in every size class it runs; FGX_DEEP_CLIPS=1: the same builds in the plain mode's classes)
+    const bool clips = !meth_dev && sw.deep_clips;
+    if (clips && size_class == 1) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<128, 128, 1>), dim3(n_list), dim3(128), 0, s, PD, DP);
+    else if (clips && size_class == 2) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    else if (clips && size_class == 3) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_CAP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
+    else if (meth_dev && size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64, 1>), dim3(n_list), dim3(64), 0, s, PD, DP);
     else if (meth_dev && size_class == 2) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
     else if (meth_dev && size_class == 3) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<256, DEEP_CAP_MAX, 1>), dim3(n_list), dim3(256), 0, s, PD, DP);
     else if (size_class == 0) FGX_LAUNCH(HIP_KERNEL_NAME(k_deep_parse<64, 64>), dim3(n_list), dim3(64), 0, s, PD, DP);
@@ -3970,6 +3991,7 @@ struct Batch {
     for (int i = 0; i < FGX_STATS_LEN; i++) res->stats[i] = h_misc[MISC_STATS + i];
     res->n_deferred = (uint32_t)(h_misc[MISC_N_DEFERRED] & 0xFFFFFFFFull);
     fp.last_meth_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] & 0xFFFFFFFFull);
+    if (!fp.canon_second_pass) fp.last_deep_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] >> 32);   // (the second pass runs no clip build outside the mode)
     if (dup_deep_ran) { fp.last_duplex_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_duplex_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
     if (codec_deep_ran) { fp.last_codec_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_codec_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
     res->d_deferred = fp.d_deferred.as<uint32_t>();

@@ -24,8 +24,8 @@
 //
 // Shape: k_simplex_wave2's record shape (simplex_wave2.inc), at most DEEP_MAX records (DEEP_CAP_MAX under --max-reads), at most 255
 // retained reads per end; no family with a fragment consensus AND a pair.  Everything else goes to k_family (up to 128 records) and
-// from there to the host path.  The methylation-aware mode's build of k_deep_parse (CLIPS 1, below) also takes reads with soft / hard clips around one
-// aligned block.
+// from there to the host path.  The CLIPS 1 builds of k_deep_parse (below) also take reads with soft / hard clips around one aligned block: the
+// methylation-aware mode launches them always, the plain mode under FGX_DEEP_CLIPS=1 (default off) in place of the CLIPS 0 builds.
 //
 // --max-reads (downsample_filtered_source_reads, vanilla_caller.rs:902-932) is decided in k_deep_parse where the family gates are taken,
 // with the counters and in the order of k_family_wave<0> and k_family (fastpath.hip): per end, after the zero-length reads are out and
@@ -210,7 +210,8 @@ __device__ __forceinline__ void deep_parse_records(const FastParams& P, Recs& S,
 // for those of more than 512 under --max-reads (an end fits its 255 reads after the cut only), <64, 64> for everything else when the streaming
 // kernels are the whole pipeline (methylation-aware mode: a wavefront per family, 3 KB of LDS)
 //
-// CLIPS 1: the build of the methylation-aware mode, which takes soft- / hard-clipped reads (H* S* (M|=|X)+ S* H*, up to WG_CIG_OPS ops) beside the
+// CLIPS 1: the build of the methylation-aware mode — and, under FGX_DEEP_CLIPS=1, of the plain mode, where it keeps taking unmapped records and counts the
+// families with a multi-op record it accepts (deep_clipped_counter) —, which takes soft- / hard-clipped reads (H* S* (M|=|X)+ S* H*, up to WG_CIG_OPS ops) beside the
 // single-op ones.  The reference calls such a read in query space like any other (create_source_read :1094-1163 keeps the soft-clipped bases), so the
 // column kernel sees no difference; what the clips change is restated here: the mate clip (bam::mate_clip on the ops), the shared span of a pair (the
 // ALIGNED blocks overlap; the leading clip goes into the query offsets) and where the anchor's columns lie on the reference (step 6).  An indel read
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
 
   // ---- 1. parse: thread = record --------------------------------------------------------------------------------------------------------
   // (DeepLds holds the per-record arrays AND the family's counters: S is both arguments; k_wide_parse passes its global arrays and its LDS counters)
-  deep_parse_records<CLIPS>(P, S, S, r0, n, tid, DEEP_NT, sTagCls, CLIPS == 0 && !P.meth_mode);
+  deep_parse_records<CLIPS>(P, S, S, r0, n, tid, DEEP_NT, sTagCls, !P.meth_mode);   // (the clip builds outside the mode — FGX_DEEP_CLIPS=1 — keep taking unmapped records)
   __syncthreads();
   if (S.bad & 1u) { leave(); return; }
   if (S.bad >> 1) {
@@ -493,7 +494,10 @@ __global__ __launch_bounds__(NT) void k_deep_parse(FastParams P, DeepParams D) {
     f.rx_len_b = (uint8_t)((ne == 2u && S.rxcnt[2]) ? S.rx_len[S.rxfirst[2]] : 0u);
     f.rej_insuf = rej_insuf; f.rej_zero = rej_zero; f.rej_orphan = rej_orphan; f.rej_down = rej_down;
     f.ov_agree = S.ov_agree; f.ov_dis = S.ov_dis; f.ov_corr = S.ov_corr;
-    if constexpr (CLIPS != 0) f.clipped = S.multi;
+    if constexpr (CLIPS != 0) {
+      f.clipped = S.multi;
+      if (S.multi && !P.meth_mode) atomicAdd(deep_clipped_counter(P), 1u);   // (FGX_DEEP_CLIPS=1; no leave() behind this point.  The mode counts in k_deep_cols<1>)
+    }
     if (P.meth_mode && P.genome) {
       auto top_of = [&](uint32_t r) { return ((S.bits[r] & 4u) != 0) == ((S.bits[r] & 32u) != 0); };   // is_top_strand (methylation.rs:392-398): reverse == LAST
       for (uint32_t k = 0; k < ne; k++) {

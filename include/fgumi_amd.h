@@ -489,6 +489,13 @@ uint32_t fgx_debug_last_codec_deep(const fgx_caller* c);
 /* ... and of how many of those molecules a --max-reads-per-strand dropped a read (the CAP builds of the record kernel, launched for a caller with
  * a cap > 0).  Always <= fgx_debug_last_codec_deep. */
 uint32_t fgx_debug_last_codec_deep_capped(const fgx_caller* c);
+/* Diagnostics of the last device batch of `c`: groups of more than 64 records — simplex families or duplex molecules — that hold a record of more than
+ * one CIGAR op (soft / hard clips around one aligned block, H* S* (M|=|X)+ S* H*, up to 16 ops) and that the clip-taking builds of the streaming record
+ * kernels (k_deep_parse<.., .., 1> outside the methylation-aware mode, k_duplex_deep_parse<.., .., .., 1>) accepted.  Those builds are launched only under
+ * FGX_DEEP_CLIPS=1 (read per batch, default off: such a group goes where it went — k_family or the deferred list): 0 with the switch unset, and in the
+ * methylation-aware mode, whose own count is fgx_debug_last_meth_clipped.  "Accepted by the record kernel": a group the column kernel hands on afterwards
+ * (an RX failure, an overflow of the item pool) stays counted. */
+uint32_t fgx_debug_last_deep_clipped(const fgx_caller* c);
 /* Repair rounds of the last fgx_record_boundaries_device call on `c` (0 = every segment's guess was right; fgx_run_bam sums them into boundary_repair_rounds). */
 uint32_t fgx_debug_last_boundary_rounds(const fgx_caller* c);
 
