@@ -87,7 +87,8 @@ EXPORTS = ["fgx_options_default", "fgx_create", "fgx_destroy", "fgx_last_error",
            "fgx_record_boundaries_device", "fgx_inflate_block_host", "fgx_inflate_block_two_phase_host", "fgx_deflate_block_host", "fgx_run_bam", "fgx_run_bam_rejects", "fgx_bgzf_inflate_device_bench", "fgx_bgzf_deflate_device_bench", "fgx_bgzf_recompress_file", "fgx_pipeline_last_error",
            "fgx_set_reference", "fgx_methylation_annotate_host", "fgx_methylation_runs_host", "fgx_methylation_mm_ml_host", "fgx_canon_duplex_host", "fgx_canon_duplex_runs_host", "fgx_canon_simplex_host", "fgx_canon_codec_host", "fgx_simplex_rejects_host", "fgx_strand_rejects_host", "fgx_balanced_shards", "fgx_regenerate_alignment_tags_host",
            "fgx_debug_last_duplex_deep", "fgx_debug_last_duplex_deep_capped", "fgx_debug_last_boundary_rounds",
-           "fgx_debug_last_codec_deep", "fgx_debug_last_codec_deep_capped", "fgx_debug_last_deep_clipped"]
+           "fgx_debug_last_codec_deep", "fgx_debug_last_codec_deep_capped", "fgx_debug_last_deep_clipped",
+           "fgx_canon_duplex_deep_host", "fgx_debug_canon_duplex_deep_device", "fgx_debug_last_deep_indels"]
 
 _lib = None
 
@@ -219,6 +220,15 @@ def load():
     if hasattr(L, "fgx_debug_last_deep_clipped"):           # (likewise: a library built before the FGX_DEEP_CLIPS builds)
         L.fgx_debug_last_deep_clipped.argtypes = [VP]
         L.fgx_debug_last_deep_clipped.restype = U32
+    if hasattr(L, "fgx_debug_last_deep_indels"):            # (likewise: a library built before FGX_DEEP_INDELS)
+        L.fgx_debug_last_deep_indels.argtypes = [VP]
+        L.fgx_debug_last_deep_indels.restype = U32
+    if hasattr(L, "fgx_canon_duplex_deep_host"):
+        L.fgx_canon_duplex_deep_host.argtypes = [VP, VP, VP, VP, U32, VP, VP, VP]
+        L.fgx_canon_duplex_deep_host.restype = I
+    if hasattr(L, "fgx_debug_canon_duplex_deep_device"):    # (defined beside the kernel: tests/apiemu's library, which links no kernel of the device pipeline, has none)
+        L.fgx_debug_canon_duplex_deep_device.argtypes = [VP, VP, U64, VP, VP, U32, VP, VP, VP, VP]
+        L.fgx_debug_canon_duplex_deep_device.restype = I
     if hasattr(L, "fgx_debug_last_boundary_rounds"):        # (likewise: a library built before this export)
         L.fgx_debug_last_boundary_rounds.argtypes = [VP]
         L.fgx_debug_last_boundary_rounds.restype = U32

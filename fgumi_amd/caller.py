@@ -352,6 +352,13 @@ class _HandleCaller(ConsensusCaller):
         the switch unset).  Counted where the record kernel accepts the group: the column kernel may still hand it on (an RX failure, a full item pool)."""
         return int(lib.fgx_debug_last_deep_clipped(self._h))
 
+    def last_deep_indel_molecules(self) -> int:
+        """Duplex molecules of more than 64 records of the last batch that hold an indel / skip / pad read and that the deep duplex kernels decided in
+        the canonical second pass, after the workgroup-per-molecule canonicaliser rewrote them (FGX_DEEP_INDELS=1, read per call; the duplex caller outside
+        the methylation-aware mode, --trim and --rejects; 0 with the switch unset).  With this switch alone a deep molecule whose only oddity is a soft clip
+        takes the same route; with FGX_DEEP_CLIPS=1 the first pass takes it and `last_deep_clipped` counts it."""
+        return int(lib.fgx_debug_last_deep_indels(self._h))
+
     def set_general_only(self, on: bool = True):
         """Route every family through the general host-orchestrated path (default: device-resident fast
         path, general path only for the families it defers)."""

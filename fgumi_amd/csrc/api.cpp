@@ -24,7 +24,7 @@ using canon::CANON_KIND_DUPLEX; using canon::CANON_KIND_CODEC; using canon::CANO
 uint32_t launch_canon_molecules(hipStream_t s, int kind, const canon::Params& P, const canon::CodecParams& PC, const uint8_t* d_blob,
                                 const uint64_t* d_rec_off, const uint32_t* d_rec_len, const uint32_t* d_grp_first, const uint32_t* d_def, uint32_t nd,
                                 const uint64_t* d_first, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int* d_status,
-                                canon::Delta* d_delta, DevBuf& slabs, canon::RefRuns* d_runs, const rej::Params* PS);
+                                canon::Delta* d_delta, DevBuf& slabs, canon::RefRuns* d_runs, const rej::Params* PS, bool deep);
 void canon_layout_device(hipStream_t s, const uint32_t* d_rec_len, const uint32_t* d_grp_first, const uint32_t* d_def, uint32_t nd, unsigned long long* work,
                          unsigned long long* d_first, DevBuf& out_off, DevBuf& scan_tmp, uint64_t* n_slots, uint64_t* bytes);
 void canon_compact_device(hipStream_t s, const int* d_status, const unsigned long long* d_first, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t nd,
@@ -408,20 +408,25 @@ int fgx_methylation_mm_ml_host(const uint8_t* bases, uint32_t n, const uint8_t* 
 // canon_core.h on the host: the canonical form of ONE duplex molecule (the records at rec_off / rec_len), written to `out` at the same
 // offsets; out_len[i] = the canonical record's length, 0 = dropped by the alignment filter.  delta5 = {reads dropped
 // (MinorityAlignment), the four CorrectionStats of the overlap pre-step}.  Returns 0, or 1 when the molecule is out of scope.
-static canon::Params canon_params(const fgx_options* o) {
-  canon::Params P;
-  P.min_bq = o->min_input_base_quality; P.overlapping = o->overlapping_consensus; P.trim = o->trim; P._pad = 0;
-  P.min_total = o->duplex_min_reads[0]; P.min_xy = o->duplex_min_reads[1]; P.min_yx = o->duplex_min_reads[2];
-  P.max_reads_per_strand = o->duplex_max_reads_per_strand;
-  P.cell_tag[0] = o->cell_tag[0]; P.cell_tag[1] = o->cell_tag[1]; P._pad2[0] = P._pad2[1] = 0;
-  return P;
-}
+static canon::Params canon_params(const fgx_options* o) { return canon_params_of(o); }   // (fastpath.h: the debug entry of canon_deep.inc shares it)
 int fgx_canon_duplex_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
                           uint64_t* delta5) {
   if (!o || o->struct_size != sizeof(fgx_options) || !blob || !out || !out_len || !delta5) return 2;
   static thread_local canon::Scratch S;
   canon::Delta D;
   const int rc = canon::canon_duplex_molecule(canon_params(o), blob, rec_off, rec_len, n, out, rec_off, out_len, S, D);
+  delta5[0] = D.minority; for (int i = 0; i < 4; i++) delta5[1 + i] = D.ov[i];
+  return rc;
+}
+// The same with the record bound at canon::DEEP_MAX_READS (512): the scalar form k_canon_duplex_deep (canon_deep.inc; FGX_DEEP_INDELS=1) is compared with, byte for
+// byte.  For molecules of up to 128 records its results are fgx_canon_duplex_host's.
+int fgx_canon_duplex_deep_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
+                               uint64_t* delta5) {
+  if (!o || o->struct_size != sizeof(fgx_options) || !blob || !out || !out_len || !delta5) return 2;
+  static thread_local std::unique_ptr<canon::DeepScratch> S;
+  if (!S) S.reset(new canon::DeepScratch());
+  canon::Delta D;
+  const int rc = canon::canon_duplex_molecule(canon_params(o), blob, rec_off, rec_len, n, out, rec_off, out_len, *S, D);
   delta5[0] = D.minority; for (int i = 0; i < 4; i++) delta5[1 + i] = D.ov[i];
   return rc;
 }
@@ -736,6 +741,15 @@ static bool codec_canon_enabled() { return opt_in("FGX_CODEC_CANON"); }
 // and k_family_wave<1, 1> / k_deep_cols<1> look a column's reference base up through the anchor's runs.  Without the switch what the first pass defers in the mode
 // is the general path's, as before; with the mode off the simplex caller's routing does not change (k_family keeps its indel families).
 static bool meth_canon_enabled() { const char* e = getenv("FGX_METH_CANON"); return e && e[0] && e[0] != '0'; }
+// FGX_DEEP_INDELS=1 (default off; read per call; it does not follow FGX_OPT_IN_ALL): deferred duplex molecules of 65 .. 512 records are canonicalised as well — by
+// k_canon_duplex_deep (canon_deep.inc), a workgroup per molecule, behind the lane kernel, which then stops at 64 records — and the deep duplex kernels
+// (duplex_deep.inc) decide them in the second pass.  The duplex caller outside the methylation-aware mode, --trim and --rejects.
+static bool deep_indels_enabled(const fgx_caller* c) {
+  const char* e = getenv("FGX_DEEP_INDELS");
+  if (!(e && e[0] && e[0] != '0')) return false;
+  return c->opt.caller_kind == FGX_CALLER_DUPLEX && c->opt.methylation_mode == FGX_METHYLATION_DISABLED && !c->opt.trim && !c->opt.track_rejects &&
+         !(c->fast && c->fast->fp.rejects_pass);
+}
 // does the canonical second pass run for this caller?
 static bool canon_pass_enabled(const fgx_caller* c) {
   const int kind = c->opt.caller_kind;
@@ -785,6 +799,7 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
   std::vector<canon::RefRuns> runs(with_runs ? n_slots : 0);
   const canon::Params P = canon_params(&c->opt);
   const canon::CodecParams PC = canon_codec_params(&c->opt);
+  const bool deep = deep_indels_enabled(c);
   c->d_canon_blob.reserve(bytes + 16);
   if (on_device) {
     // FGX_CANON_DEVICE=1: a lane per molecule over the records hybrid_upload already put on the device (canon_device.hip); the
@@ -802,7 +817,7 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
     hip_check(hipMemcpyAsync(a + o_def, def.data(), nd * 4, hipMemcpyHostToDevice, s), "H2D deferred groups");
     launch_canon_molecules(s, kind, P, PC, c->d_in_blob.as<uint8_t>(), c->d_in_off.as<uint64_t>(), c->d_in_len.as<uint32_t>(), c->d_in_grp.as<uint32_t>(),
                            (const uint32_t*)(a + o_def), (uint32_t)nd, (const uint64_t*)(a + o_first), c->d_canon_blob.as<uint8_t>(), (const uint64_t*)(a + o_off),
-                           (uint32_t*)(a + o_len), (int*)(a + o_status), (canon::Delta*)(a + o_delta), c->d_canon_slabs, with_runs ? (canon::RefRuns*)(a + o_runs) : nullptr, &PS);
+                           (uint32_t*)(a + o_len), (int*)(a + o_status), (canon::Delta*)(a + o_delta), c->d_canon_slabs, with_runs ? (canon::RefRuns*)(a + o_runs) : nullptr, &PS, deep);
     if (with_runs && n_slots) hip_check(hipMemcpyAsync(runs.data(), a + o_runs, runs.size() * sizeof(canon::RefRuns), hipMemcpyDeviceToHost, s), "D2H reference runs");
     hip_check(hipMemcpyAsync(status.data(), a + o_status, nd * 4, hipMemcpyDeviceToHost, s), "D2H canonical status");
     hip_check(hipMemcpyAsync(out_len.data(), a + o_len, n_slots * 4, hipMemcpyDeviceToHost, s), "D2H canonical lengths");
@@ -812,7 +827,8 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
     unsigned T = host_threads();
     if (T > nd / 64 + 1) T = (unsigned)(nd / 64 + 1);
     auto work = [&](unsigned t) {
-      std::unique_ptr<canon::Scratch> S(kind == CANON_KIND_DUPLEX ? new canon::Scratch() : nullptr);
+      std::unique_ptr<canon::Scratch> S(kind == CANON_KIND_DUPLEX && !deep ? new canon::Scratch() : nullptr);
+      std::unique_ptr<canon::DeepScratch> SD(kind == CANON_KIND_DUPLEX && deep ? new canon::DeepScratch() : nullptr);   // (FGX_DEEP_INDELS=1: the scalar form at 512 records)
       std::unique_ptr<canon::CodecScratch> SC(codec ? new canon::CodecScratch() : nullptr);
       std::unique_ptr<rej::Scratch> SS(kind == CANON_KIND_SIMPLEX ? new rej::Scratch() : nullptr);
       for (size_t k = t; k < nd; k += T) {
@@ -823,6 +839,7 @@ static void canon_second_pass(fgx_caller* c, const uint8_t* records, const uint6
           continue;
         }
         status[k] = codec ? canon::canon_codec_molecule(PC, records, rec_off + r0, rec_len + r0, n, blob.data(), out_off.data() + first[k], out_len.data() + first[k], *SC)
+                          : deep ? canon::canon_duplex_molecule(P, records, rec_off + r0, rec_len + r0, n, blob.data(), out_off.data() + first[k], out_len.data() + first[k], *SD, delta[k])
                           : canon::canon_duplex_molecule(P, records, rec_off + r0, rec_len + r0, n, blob.data(), out_off.data() + first[k], out_len.data() + first[k], *S, delta[k],
                                                           with_runs ? runs.data() + first[k] : nullptr);
       }
@@ -1060,7 +1077,7 @@ static bool canon_resident_pass(fgx_caller* c, const uint8_t* d_blob, const uint
   if (with_runs) c->d_canon_runs.reserve((size_t)(n_slots + 1) * sizeof(canon::RefRuns));
   canon::RefRuns* const d_runs = with_runs ? c->d_canon_runs.as<canon::RefRuns>() : nullptr;
   launch_canon_molecules(s, canon_kind(c), canon_params(&c->opt), canon_codec_params(&c->opt), d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, (const uint64_t*)d_first,
-                         c->d_canon_blob.as<uint8_t>(), c->d_res_outoff.as<uint64_t>(), d_out_len, d_status, d_delta, c->d_canon_slabs, d_runs, &PS);
+                         c->d_canon_blob.as<uint8_t>(), c->d_res_outoff.as<uint64_t>(), d_out_len, d_status, d_delta, c->d_canon_slabs, d_runs, &PS, deep_indels_enabled(c));
   uint32_t n_cg = 0, n_cr = 0;
   canon_compact_device(s, d_status, d_first, c->d_res_outoff.as<uint64_t>(), d_out_len, nd, work, c->d_canon_off, c->d_canon_len, c->d_canon_grp, c->d_res_cdef, c->d_res_scan,
                        &n_cg, &n_cr, d_runs, &c->d_canon_cruns);
@@ -1504,6 +1521,7 @@ uint32_t fgx_debug_last_meth_device(const fgx_caller* c) { return (c && c->fast)
 // there, read back with the batch's other counters
 uint32_t fgx_debug_last_meth_clipped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_meth_clipped : 0u; }
 uint32_t fgx_debug_last_deep_clipped(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_clipped : 0u; }
+uint32_t fgx_debug_last_deep_indels(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_indels : 0u; }
 uint32_t fgx_debug_last_deep_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_deep_families : 0u; }
 uint32_t fgx_debug_last_wide_families(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_wide_families : 0u; }
 uint32_t fgx_debug_last_duplex_deep(const fgx_caller* c) { return (c && c->fast) ? c->fast->fp.last_duplex_deep : 0u; }

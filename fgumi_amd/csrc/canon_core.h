@@ -43,6 +43,7 @@ namespace fgx {
 namespace canon {
 
 constexpr uint32_t MAX_READS = 128;
+constexpr uint32_t DEEP_MAX_READS = 512;        // the deep form (FGX_DEEP_INDELS=1: k_canon_duplex_deep, canon_deep.inc, and its scalar twin): same rules, four times the records
 constexpr uint32_t MAX_OPS = 16;
 constexpr uint32_t MAX_GROUPS = 16;
 constexpr int32_t OTHER_REF_XOR = 0x20000000;   // R2 records of the canonical molecule: ref_id ^ this
@@ -73,12 +74,14 @@ struct ReadInfo {
   uint8_t n_simp;
   SimpOp simp[MAX_OPS];  // simplified CIGAR, reversed for reverse reads, truncated to final_len
 };
-struct Scratch {
-  ReadInfo r[MAX_READS];
-  uint32_t list[MAX_READS];      // one alignment-filter set, in source order, then sorted by length
+template <uint32_t MAXR> struct ScratchT {   // MAXR: the record bound of the form (a multiple of 64)
+  ReadInfo r[MAXR];
+  uint32_t list[MAXR];           // one alignment-filter set, in source order, then sorted by length
   uint32_t mc_ops[MAX_OPS + 1];
   uint32_t ops[MAX_OPS];
 };
+using Scratch = ScratchT<MAX_READS>;
+using DeepScratch = ScratchT<DEEP_MAX_READS>;   // 77 KB: the scalar form at 512 records (host hook, stand-in of the emulation); the device kernel keeps its own state in LDS
 struct Delta {
   uint64_t minority;             // reads dropped by the alignment filter (MinorityAlignment; also total_reads / filtered_reads)
   uint64_t ov[4];                // CorrectionStats of the overlap pre-step
@@ -240,9 +243,10 @@ CANON_HD int simp_cmp(const SimpOp* a, uint32_t na, const SimpOp* b, uint32_t nb
 
 // The alignment filter over S.list[0 .. n) (indices into S.r, source order).  Clears `keep` of the rejected reads; returns their
 // count, or -1 when there are more than MAX_GROUPS groups.
-CANON_HD int alignment_filter(Scratch& S, uint32_t n) {
+template <uint32_t MAXR> CANON_HD int alignment_filter(ScratchT<MAXR>& S, uint32_t n) {
+  static_assert(MAXR % 64 == 0, "the membership mask is MAXR / 64 words");
   if (n < 2) return 0;
-  // stable sort by length, longest first (insertion sort: n <= 128)
+  // stable sort by length, longest first (insertion sort: n <= MAXR)
   for (uint32_t i = 1; i < n; i++) {
     const uint32_t v = S.list[i];
     uint32_t j = i;
@@ -250,7 +254,7 @@ CANON_HD int alignment_filter(Scratch& S, uint32_t n) {
     S.list[j] = v;
   }
   uint32_t g_rep[MAX_GROUPS], g_size[MAX_GROUPS];
-  uint64_t g_mem[MAX_GROUPS][2];
+  uint64_t g_mem[MAX_GROUPS][MAXR / 64];
   uint32_t ng = 0;
   for (uint32_t i = 0; i < n; i++) {
     const ReadInfo& R = S.r[S.list[i]];
@@ -261,7 +265,7 @@ CANON_HD int alignment_filter(Scratch& S, uint32_t n) {
     }
     if (!found) {
       if (ng == MAX_GROUPS) return -1;
-      g_rep[ng] = i; g_size[ng] = 1; g_mem[ng][0] = g_mem[ng][1] = 0; g_mem[ng][i >> 6] |= 1ull << (i & 63);
+      g_rep[ng] = i; g_size[ng] = 1; for (uint32_t w = 0; w < MAXR / 64; w++) g_mem[ng][w] = 0; g_mem[ng][i >> 6] |= 1ull << (i & 63);
       ng++;
     }
   }
@@ -333,10 +337,11 @@ CANON_HD uint32_t rewrite_record(uint8_t* rec, uint32_t n, uint32_t clip, bool m
 // One duplex molecule: records `n` at rec_off / rec_len in `blob` → canonical records in `out` at out_off[i] (room for rec_len[i]
 // bytes each), out_len[i] = new length, 0 = the record is dropped.  Returns CANON_OK or CANON_OUT_OF_SCOPE (outputs undefined).
 // `runs` (methylation-aware mode, else null): runs[i] = the reference runs of surviving record i.
-CANON_HD int canon_duplex_molecule(const Params& P, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out,
-                                   const uint64_t* out_off, uint32_t* out_len, Scratch& S, Delta& D, RefRuns* runs = nullptr) {
+// MAXR (deduced from the scratch): the record bound — MAX_READS for the lane kernels and fgx_canon_duplex_host, DEEP_MAX_READS for the deep form.
+template <uint32_t MAXR> CANON_HD int canon_duplex_molecule(const Params& P, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out,
+                                                            const uint64_t* out_off, uint32_t* out_len, ScratchT<MAXR>& S, Delta& D, RefRuns* runs = nullptr) {
   D.minority = 0; D.ov[0] = D.ov[1] = D.ov[2] = D.ov[3] = 0;
-  if (n == 0 || n > MAX_READS || P.trim) return CANON_OUT_OF_SCOPE;
+  if (n == 0 || n > MAXR || P.trim) return CANON_OUT_OF_SCOPE;
   if (P.min_xy > P.min_total || P.min_yx > P.min_xy) return CANON_OUT_OF_SCOPE;          // the reference refuses the options
   bool has_a = false, has_b = false;
   for (uint32_t i = 0; i < n; i++) {
@@ -422,7 +427,11 @@ CANON_HD int canon_duplex_molecule(const Params& P, const uint8_t* blob, const u
     for (uint32_t k = 0; k < nc; k++) {
       const uint32_t t = S.ops[k] & 0xF;
       const uint8_t kk = (t == 4 || t == 5 || t == 7 || t == 8) ? (uint8_t)0 : (uint8_t)t;
-      if (nt && tmp[nt - 1].k == kk) tmp[nt - 1].len += S.ops[k] >> 4;
+      if (nt && tmp[nt - 1].k == kk) {
+        tmp[nt - 1].len += S.ops[k] >> 4;
+        // (the deep form alone: k_canon_duplex_deep keeps a simplified op as `len << 4 | kind`, so both refuse a merged op that does not fit 28 bits)
+        if (MAXR > MAX_READS && tmp[nt - 1].len >= (1u << 28)) return CANON_OUT_OF_SCOPE;
+      }
       else { tmp[nt].k = kk; tmp[nt].len = S.ops[k] >> 4; nt++; }
     }
     uint32_t remaining = fl;

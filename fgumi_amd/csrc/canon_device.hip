@@ -15,6 +15,8 @@
 #include "engine.h"
 #include "canon_core.h"
 #include "reject_core.h"
+#include "fastpath.h"
+#include <memory>
 #ifndef FGX_DEVEMU            // (tests/devemu compiles this file for the host with a serial scan)
 #include <hipcub/hipcub.hpp>
 #endif
@@ -34,11 +36,13 @@ __global__ void __launch_bounds__(CANON_BLOCK)
 k_canon_duplex(canon::Params P, const uint8_t* __restrict__ blob, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ rec_len,
                const uint32_t* __restrict__ grp_first, const uint32_t* __restrict__ def, uint32_t nd, const uint64_t* __restrict__ first,
                uint8_t* out, const uint64_t* __restrict__ out_off, uint32_t* out_len, int* status, canon::Delta* delta, canon::Scratch* slabs,
-               canon::RefRuns* runs) {                      // (methylation-aware mode, else null: the reference runs of every slot)
+               canon::RefRuns* runs,                        // (methylation-aware mode, else null: the reference runs of every slot)
+               uint32_t max_n) {                            // molecules of more records are another kernel's (FGX_DEEP_INDELS=1: 64, k_canon_duplex_deep takes them; else no bound)
   const uint32_t lane = blockIdx.x * CANON_BLOCK + threadIdx.x, stride = gridDim.x * CANON_BLOCK;
   canon::Scratch& S = slabs[lane];
   for (uint32_t k = lane; k < nd; k += stride) {
     const uint32_t r0 = grp_first[def[k]], n = grp_first[def[k] + 1] - r0;
+    if (n > max_n) continue;
     canon::Delta D;
     const int st = canon::canon_duplex_molecule(P, blob, rec_off + r0, rec_len + r0, n, out, out_off + first[k], out_len + first[k], S, D, runs ? runs + first[k] : nullptr);
     status[k] = st;
@@ -81,11 +85,29 @@ k_canon_simplex(rej::Params P, const uint8_t* __restrict__ blob, const uint64_t*
 // Launches the canonicalisation of the `nd` deferred molecules def[0..nd) of the batch at d_blob / d_rec_off / d_rec_len / d_grp_first.
 // d_first[k] = first record slot of molecule k in d_out_off / d_out_len (the caller laid the slots out); results stay on the device.
 // `kind`: CANON_KIND_DUPLEX (0), CANON_KIND_CODEC (1) or CANON_KIND_SIMPLEX (2, with its parameters in `PS`).  `slabs` is grown as needed.  `d_runs` (duplex and simplex in the methylation-aware mode, else null): room for one canon::RefRuns per slot.  Returns the number of lanes launched.
+// `deep` (FGX_DEEP_INDELS=1; duplex outside the methylation-aware mode): the lane kernel leaves the molecules of more than 64 records to k_canon_duplex_deep
+// (canon_deep.inc), a workgroup per molecule up to 512 records, launched behind it over the same list.
+#ifdef FGX_DEVEMU
+// (tests/apiemu links this file without fastpath.hip: a stand-in of the launcher that runs the scalar form at 512 records a molecule at a time; the wave emulator
+// and the product link fastpath.hip, whose definition — the kernel — takes its place)
+__attribute__((weak)) void launch_canon_duplex_deep(hipStream_t, const canon::Params& P, const uint8_t* d_blob, const uint64_t* d_rec_off, const uint32_t* d_rec_len,
+                                                    const uint32_t* d_grp_first, const uint32_t* d_def, uint32_t nd, const uint64_t* d_first, uint8_t* d_out,
+                                                    const uint64_t* d_out_off, uint32_t* d_out_len, int* d_status, canon::Delta* d_delta) {
+  std::unique_ptr<canon::DeepScratch> S(new canon::DeepScratch());
+  for (uint32_t k = 0; k < nd; k++) {
+    const uint32_t r0 = d_grp_first[d_def[k]], n = d_grp_first[d_def[k] + 1] - r0;
+    if (n <= 64u) continue;
+    d_status[k] = canon::canon_duplex_molecule(P, d_blob, d_rec_off + r0, d_rec_len + r0, n, d_out, d_out_off + d_first[k], d_out_len + d_first[k], *S, d_delta[k]);
+    if (d_status[k] == canon::CANON_OK) for (uint32_t i = 0; i < n; i++) if (d_out_len[d_first[k] + i]) canon::wr32(d_out + d_out_off[d_first[k] + i] - 4, d_out_len[d_first[k] + i]);
+  }
+}
+#endif
 uint32_t launch_canon_molecules(hipStream_t s, int kind, const canon::Params& P, const canon::CodecParams& PC, const uint8_t* d_blob,
                                 const uint64_t* d_rec_off, const uint32_t* d_rec_len, const uint32_t* d_grp_first, const uint32_t* d_def, uint32_t nd,
                                 const uint64_t* d_first, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int* d_status,
-                                canon::Delta* d_delta, DevBuf& slabs, canon::RefRuns* d_runs = nullptr, const rej::Params* PS = nullptr) {
+                                canon::Delta* d_delta, DevBuf& slabs, canon::RefRuns* d_runs = nullptr, const rej::Params* PS = nullptr, bool deep = false) {
   if (nd == 0) return 0;
+  deep = deep && kind == CANON_KIND_DUPLEX && !d_runs;
   const bool codec = kind == CANON_KIND_CODEC, simplex = kind == CANON_KIND_SIMPLEX;
   uint32_t blocks = (nd + CANON_BLOCK - 1) / CANON_BLOCK;
   if (blocks > CANON_MAX_LANES / CANON_BLOCK) blocks = CANON_MAX_LANES / CANON_BLOCK;
@@ -99,8 +121,9 @@ uint32_t launch_canon_molecules(hipStream_t s, int kind, const canon::Params& P,
                        d_out_len, d_status, slabs.as<canon::CodecScratch>());
   else
     hipLaunchKernelGGL(k_canon_duplex, dim3(blocks), dim3(CANON_BLOCK), 0, s, P, d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, d_first, d_out, d_out_off,
-                       d_out_len, d_status, d_delta, slabs.as<canon::Scratch>(), d_runs);
+                       d_out_len, d_status, d_delta, slabs.as<canon::Scratch>(), d_runs, deep ? 64u : 0xFFFFFFFFu);
   hip_check(hipGetLastError(), "k_canon launch");
+  if (deep) launch_canon_duplex_deep(s, P, d_blob, d_rec_off, d_rec_len, d_grp_first, d_def, nd, d_first, d_out, d_out_off, d_out_len, d_status, d_delta);
   return lanes;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <algorithm>
 #include "engine.h"
+#include "canon_core.h"
 
 // (small rules shared by kernels and host code)
 #if defined(__HIPCC__)
@@ -11,6 +12,21 @@
 #endif
 
 namespace fgx {
+
+// the canonical pass's parameters out of a caller's options (api.cpp; the debug entry of canon_deep.inc)
+inline canon::Params canon_params_of(const fgx_options* o) {
+  canon::Params P;
+  P.min_bq = o->min_input_base_quality; P.overlapping = o->overlapping_consensus; P.trim = o->trim; P._pad = 0;
+  P.min_total = o->duplex_min_reads[0]; P.min_xy = o->duplex_min_reads[1]; P.min_yx = o->duplex_min_reads[2];
+  P.max_reads_per_strand = o->duplex_max_reads_per_strand;
+  P.cell_tag[0] = o->cell_tag[0]; P.cell_tag[1] = o->cell_tag[1]; P._pad2[0] = P._pad2[1] = 0;
+  return P;
+}
+// FGX_DEEP_INDELS=1 (canon_deep.inc; the kernel lives in the fastpath.hip translation unit): the canonical form of the deferred duplex molecules of 65 .. 512 records, a
+// workgroup per molecule.  Same arrays as launch_canon_molecules (canon_device.hip), which calls it behind its lane kernel; molecules of up to 64 records are skipped.
+void launch_canon_duplex_deep(hipStream_t s, const canon::Params& P, const uint8_t* d_blob, const uint64_t* d_rec_off, const uint32_t* d_rec_len, const uint32_t* d_grp_first,
+                              const uint32_t* d_def, uint32_t nd, const uint64_t* d_first, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int* d_status,
+                              canon::Delta* d_delta);
 
 constexpr int FAST_RX_CAP = 48;   // longest RX value handled on the device (longer → general path)
 
@@ -318,7 +334,8 @@ struct FastPath {
   uint32_t last_codec_deep = 0;            // CODEC molecules of more than 64 records that k_codec_deep_parse + k_codec_deep_cols (codec_deep.inc; FGX_CODEC_DEEP=1) decided in the
                                            // last batch; likewise not counted into the simplex path's counters.  They use d_big, the d_deep_* buffers and d_deep_walk (the RX list).
   uint32_t last_codec_deep_capped = 0;     // ... of which a --max-reads-per-strand dropped a read (the CAP builds of the record kernel)
-  bool canon_second_pass = false;          // set by the caller around the `run` of a canonical second pass: duplex_deep.inc and codec_deep.inc stay off there
+  bool canon_second_pass = false;          // set by the caller around the `run` of a canonical second pass: codec_deep.inc stays off there, and duplex_deep.inc unless FGX_DEEP_INDELS=1
+  uint32_t last_deep_indels = 0;           // FGX_DEEP_INDELS=1: molecules of more than 64 records that the deep duplex kernels decided in the canonical SECOND pass of the last batch
   bool rejects_pass = false;               // set by the host entry around the device pass of a --rejects batch (which runs with the option cleared): off there too
   uint32_t last_wide_families = 0;         // ... and of what those left, the wide kernels (simplex_wide.inc; FGX_DEEP_WIDE=1) took — not counted into last_deep_families
   DevBuf d_wide_scratch, d_wide_pass, d_wide_pass0, d_wide_depth;   // k_wide_parse's per-record state, the families' column passes and their scan, the passes' depth extremes

@@ -2914,6 +2914,8 @@ __global__ void k_reduce_stats(const unsigned long long* __restrict__ slots, uns
 
 }  // namespace
 
+#include "canon_deep.inc"
+
 // -----------------------------------------------------------------------------------------------------
 // host driver
 // -----------------------------------------------------------------------------------------------------
@@ -3012,6 +3014,8 @@ struct BatchSwitches {     // read at the start of every batch: tests and tools 
   const bool codec_deep = codec_deep_env && codec_deep_env[0] && codec_deep_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): CODEC molecules of more than 64 records on the device (codec_deep.inc)
   const char* const deep_clips_env = getenv("FGX_DEEP_CLIPS");
   const bool deep_clips = deep_clips_env && deep_clips_env[0] && deep_clips_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the clip-taking builds of k_deep_parse (plain mode) and k_duplex_deep_parse
+  const char* const deep_indels_env = getenv("FGX_DEEP_INDELS");
+  const bool deep_indels = deep_indels_env && deep_indels_env[0] && deep_indels_env[0] != '0';   // default OFF (it does not follow FGX_OPT_IN_ALL): the deep duplex kernels also in the canonical second pass (canon_deep.inc feeds it)
   const uint32_t seg_bytes = env_in(fgx_knob("FGX_SEG_BYTES"), 4096, 32768, 11776) & ~63u;   // 4 wavefronts x 11776 B + the static tables = 3 workgroups per CU
   const uint32_t wave_bytes = env_in(fgx_knob("FGX_WAVE_BYTES"), 1024, 22016, 0) & ~15u;     // tuning knobs (0: the FastPath's own value)
   const uint32_t lds_tile_large = env_in(fgx_knob("FGX_LDS_TILE_LARGE"), 16384, 163840, 0) & ~15u;
@@ -3084,8 +3088,9 @@ struct Batch {
   const bool meth_dup = duplex && meth_on;
   const bool dup_cap = duplex && o.duplex_max_reads_per_strand > 0;   // the CAP builds of k_family_wave<1> and of the duplex record writers
   // Duplex molecules of more than 64 records (duplex_deep.inc): k_family_wave<1> lists them instead of deferring them, and k_duplex_deep_parse +
-  // k_duplex_deep_cols decide the list.  Not under --trim or --rejects, not in the methylation-aware mode, not in the canonical second pass (FGX_DUPLEX_DEEP=0: off)
-  const bool dup_deep = duplex && sw.duplex_deep && !o.trim && !o.track_rejects && !fp.rejects_pass && !meth_dup && !fp.canon_second_pass;
+  // k_duplex_deep_cols decide the list.  Not under --trim or --rejects, not in the methylation-aware mode, and in the canonical second pass only with
+  // FGX_DEEP_INDELS=1, where the canonical molecules of 65 .. 512 records are theirs (FGX_DUPLEX_DEEP=0: off)
+  const bool dup_deep = duplex && sw.duplex_deep && !o.trim && !o.track_rejects && !fp.rejects_pass && !meth_dup && (!fp.canon_second_pass || sw.deep_indels);
   // ... and their CAP builds, which decide a --max-reads-per-strand that bites a set of such a molecule (FGX_DUPLEX_DEEP_CAP=1; off: it is deferred)
   const bool dup_deep_cap = dup_deep && dup_cap && sw.duplex_deep_cap;
   // CODEC molecules of more than 64 records (codec_deep.inc; FGX_CODEC_DEEP=1): k_family_wave<2> lists them instead of deferring them, and k_codec_deep_parse +
@@ -3162,7 +3167,7 @@ struct Batch {
   // ---- buffers, counters, events ----
   void set_up() {
     fp.last_meth_device = 0; fp.last_meth_clipped = 0; fp.last_direct = 0; fp.last_split_chunks = 0;
-    if (!fp.canon_second_pass) fp.last_deep_clipped = fp.last_duplex_deep = fp.last_duplex_deep_capped = fp.last_codec_deep = fp.last_codec_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
+    if (!fp.canon_second_pass) fp.last_deep_indels = fp.last_deep_clipped = fp.last_duplex_deep = fp.last_duplex_deep_capped = fp.last_codec_deep = fp.last_codec_deep_capped = 0;   // (the second pass belongs to the batch whose first pass counted)
     fp.last_routed = 0; fp.last_big_families = 0; fp.last_deep_families = 0; fp.last_wide_families = 0; fp.last_packed_families = 0; fp.last_classic_families = 0; fp.last_packed_clean = 0; fp.last_packed_general = 0; for (uint64_t& v : fp.last_packed_overlap) v = 0; for (uint64_t& v : fp.last_full_results) v = 0; fp.last_split_build = 0; fp.last_first_stage_retries = 0;
     fp.d_ends.reserve((size_t)n_slots * (duplex ? sizeof(DuplexDesc) : codec ? sizeof(CodecDesc) : sizeof(EndDesc)));
     fp.d_sizes.reserve(((size_t)n_slots + 1) * 8);            // (+ 1: a zero behind the last size, so that the scan's last element IS the total — one small copy fewer per step)
@@ -3992,7 +3997,8 @@ struct Batch {
     res->n_deferred = (uint32_t)(h_misc[MISC_N_DEFERRED] & 0xFFFFFFFFull);
     fp.last_meth_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] & 0xFFFFFFFFull);
     if (!fp.canon_second_pass) fp.last_deep_clipped = (uint32_t)(h_misc[MISC_N_METH_CLIPPED] >> 32);   // (the second pass runs no clip build outside the mode)
-    if (dup_deep_ran) { fp.last_duplex_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_duplex_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
+    if (dup_deep_ran && fp.canon_second_pass) fp.last_deep_indels = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull);   // (FGX_DEEP_INDELS=1; fgx_debug_last_duplex_deep stays the first pass's count)
+    else if (dup_deep_ran) { fp.last_duplex_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_duplex_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
     if (codec_deep_ran) { fp.last_codec_deep = (uint32_t)(h_misc[MISC_N_DEEP] & 0xFFFFFFFFull); fp.last_codec_deep_capped = (uint32_t)(h_misc[MISC_N_DEEP] >> 32); }
     res->d_deferred = fp.d_deferred.as<uint32_t>();
     res->d_out_off = fp.d_offsets.as<uint64_t>();

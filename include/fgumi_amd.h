@@ -222,6 +222,18 @@ int fgx_methylation_mm_ml_host(const uint8_t* bases, uint32_t n, const uint8_t* 
  * source compiles for the device (one lane per molecule). */
 int fgx_canon_duplex_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
                           uint64_t* delta5);
+/* The same with the record bound at 512 instead of 128 (canon::DEEP_MAX_READS; 16 ops, 16 alignment groups and every other out-of-scope condition as above; a
+ * simplified CIGAR op of 2^28 bases or more is refused): the scalar form of the workgroup-per-molecule kernel k_canon_duplex_deep (fgumi_amd/csrc/canon_deep.inc),
+ * which canonicalises the deferred duplex molecules of 65 .. 512 records under FGX_DEEP_INDELS=1 and is compared with this function byte for byte.  For a molecule
+ * of up to 128 records the results are fgx_canon_duplex_host's; that function keeps refusing above 128. */
+int fgx_canon_duplex_deep_host(const fgx_options* o, const uint8_t* blob, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n, uint8_t* out, uint32_t* out_len,
+                               uint64_t* delta5);
+/* Test entry of that kernel: ONE molecule of 65 .. 512 records in HOST arrays (the blob of `records_len` bytes, rec_off[i] >= 4) through k_canon_duplex_deep on the
+ * device of `o`.  `out` (records_len bytes) receives the canonical records at the records' own offsets, each kept record behind its 4-byte length prefix, as the
+ * canonical blob of the second pass holds them; out_len / delta5 as above; *status = 0, or 1 = out of scope.  Returns 0; 2 = bad arguments (also: a molecule of
+ * up to 64 records, which is the lane kernel's); 3 = a runtime error. */
+int fgx_debug_canon_duplex_deep_device(const fgx_options* o, const uint8_t* blob, uint64_t records_len, const uint64_t* rec_off, const uint32_t* rec_len, uint32_t n,
+                                       uint8_t* out, uint32_t* out_len, uint64_t* delta5, int* status);
 /* The same, with the REFERENCE RUNS the canonical pass emits in the methylation-aware mode (FGX_METH_CANON=1): for every surviving record i,
  * runs[i * FGX_CANON_RUNS_WORDS ..] = {original ref_id (-1: no position), number of runs | REVERSE bit << 31, then per run: first column, length,
  * reference position of the first column (int64, low dword first)} — query_to_ref_positions (methylation.rs:116-178) on the ORIGINAL record, the
@@ -496,6 +508,13 @@ uint32_t fgx_debug_last_codec_deep_capped(const fgx_caller* c);
  * methylation-aware mode, whose own count is fgx_debug_last_meth_clipped.  "Accepted by the record kernel": a group the column kernel hands on afterwards
  * (an RX failure, an overflow of the item pool) stays counted. */
 uint32_t fgx_debug_last_deep_clipped(const fgx_caller* c);
+/* Diagnostics of the last batch of `c`: duplex molecules of more than 64 records that the deep duplex kernels (duplex_deep.inc) decided in the CANONICAL SECOND
+ * PASS — molecules with an indel / skip / pad (or, with this switch alone, a soft-clipped) read that k_canon_duplex_deep rewrote.  Only under FGX_DEEP_INDELS=1
+ * (read per call, default off, it does not follow FGX_OPT_IN_ALL; the duplex caller outside the methylation-aware mode, --trim and --rejects): 0 with the switch
+ * unset.  fgx_debug_last_duplex_deep keeps its meaning, the first pass's count; fgx_debug_last_deferral's canonical count includes these molecules.  Still
+ * deferred: more than 512 records / 16 CIGAR ops / 16 alignment groups, a --max-reads-per-strand that bites, and what the deep kernels themselves refuse (more than
+ * 255 retained reads per record side, a read clipped to nothing). */
+uint32_t fgx_debug_last_deep_indels(const fgx_caller* c);
 /* Repair rounds of the last fgx_record_boundaries_device call on `c` (0 = every segment's guess was right; fgx_run_bam sums them into boundary_repair_rounds). */
 uint32_t fgx_debug_last_boundary_rounds(const fgx_caller* c);
 
